@@ -6,6 +6,12 @@ Workloads (BASELINE.json configs):
   selfplay — config 3/4: AlphaZero self-play, 256 concurrent 4-player 20x20 games per GPU,
              100 MCTS simulations per move, ResNet leaf evaluation; metric = MCTS sims/s.
 
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) sets up the self-play workload, warms up,
+times N plies and prints the line (metric, value, unit, ms_per_step, ...); `--dump-outputs DIR`
+also writes the last timed ply's outputs as DIR/<name>.npy. `--full` adds everything else: stage
+times, rooflines and the late game of the self-play line, the other workloads' legs and the CPU
+baselines.
+
 Multi-GPU: one process per GPU (torchrun); every rank runs its own independent shard (boards /
 games seeded by rank), no data-path collective; value = units of all ranks / max-over-ranks time.
 """
@@ -467,6 +473,8 @@ def bench_legal(args, world, rank):
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline_legal(states, args.cpu_seconds, args.cpu_pool, args.cpu_workers)
     out["_states"] = states
+    if args.dump_outputs and args.workload == "legal":
+        out["_outputs"] = legal_outputs(masks, counts)
     return out
 
 
@@ -922,7 +930,7 @@ def ppo_update_subprocess(args):
     import subprocess
 
     cmd = [sys.executable, os.path.abspath(__file__), "--workload", "ppo", "--ppo-updates", str(args.ppo_updates),
-           "--envs", str(args.envs)] + (["--no-cpu-baseline"] if args.no_cpu_baseline else [])
+           "--envs", str(args.envs), "--full"] + (["--no-cpu-baseline"] if args.no_cpu_baseline else [])
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR",
                                                             "MASTER_PORT", "BK_DIST_BACKEND")}
     env["MIOPEN_FIND_MODE"] = "FAST"
@@ -936,11 +944,114 @@ def ppo_update_subprocess(args):
         return {"error": f"timed out after {args.ppo_timeout} s"}
 
 
+def dump_outputs(dirname: str, outputs: dict) -> None:
+    """--dump-outputs: every tensor of `outputs` (what the last timed step handed its caller) as
+    <dirname>/<name>.npy in float32. Every value written is an integer below 2^24 or already a
+    float32, so the files hold the outputs exactly and two builds compare output for output."""
+    os.makedirs(dirname, exist_ok=True)
+    total = 0
+    for name, t in outputs.items():
+        a = np.ascontiguousarray(t.detach().cpu().numpy().astype(np.float32))
+        total += a.nbytes
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    assert total <= 64 << 20, f"--dump-outputs wrote {total} bytes"
+
+
+def legal_outputs(masks: torch.Tensor, counts: torch.Tensor, rows: int = 512) -> dict:
+    """The legal workload's outputs for --dump-outputs: every board's count, and the bitmasks of a
+    fixed sample (default_rng(0)) of `rows` boards as 16-bit words, low word first."""
+    B = masks.shape[0]
+    pick = torch.from_numpy(np.sort(np.random.default_rng(0).choice(B, size=min(B, rows), replace=False)))
+    words = masks.cpu()[pick].contiguous().view(torch.int16).to(torch.int32) & 0xFFFF
+    return {"counts": counts, "mask_rows": pick, "mask_words16": words}
+
+
+def selfplay_full_legs(out, args, world, rank):
+    """--full on the self-play line: the committed profiles' figures beside the live rooflines, and for
+    --workload all the other legs (exact-f32 net, uninformed MCTS, legal moves, vector env, learner,
+    7x7 config 1, PPO updates) and the CPU baselines, each a run of its own after the timed window."""
+    from blokus_rl_amd.alphazero.selfplay_bench import run_selfplay
+
+    sr = out.get("search_roofline", {})
+    if "k_leaf_step" in sr.get("kernel", ""):
+        # the leaf step's time over the timed window: the average over the window's launches in
+        # the committed kernel trace of this same command (profiles/r06_window_trace.json,
+        # tools/window_avg.py), beside this run's live sample after the window; HBM-side bytes
+        # per launch from the committed PMC passes over the same window: the fraction of the
+        # HBM roofline it draws (committed profiles, named as such)
+        sr["k_leaf_step_us_live_after_window"] = sr.pop("k_leaf_step_us", None)
+        win = _window_trace("k_leaf_step_ov", args)
+        sr["k_leaf_step_us"] = win["window_avg_us"] if win else sr["k_leaf_step_us_live_after_window"]
+        sr["k_leaf_step_us_source"] = (f"kernel-trace average over the window's {win['window_dispatches']} "
+                                       f"launches, {win['source']}" if win else "live sample after the window")
+        tr, src = _pmc_traffic("k_leaf_step_ov", args.games, with_source=True)
+        sr["traffic"], sr["traffic_source"] = tr, src
+        if tr and sr.get("k_leaf_step_us"):
+            sr["achieved_est"] = tr / (sr["k_leaf_step_us"] * 1e-6) / 1e9
+            sr["frac_est"] = sr["achieved_est"] / sr["peak"]
+    tw = _window_trace("k_leafnet_x3", args)
+    if tw and "tower_roofline" in out:
+        out["tower_roofline"]["kernel_ms_window_trace"] = tw["window_avg_us"] / 1e3
+        out["tower_roofline"]["kernel_ms_window_trace_source"] = tw["source"]
+    kname = out["roofline"].get("kernel", "").split(" ")[0]
+    if kname.startswith("k_conv3x3") or kname.startswith("k_tower") or kname.startswith("k_leafnet"):
+        # HBM bytes per launch from the committed PMC passes (profiles/r01_pmc_conv*.json)
+        out["roofline"]["traffic"], out["roofline"]["traffic_source"] = _pmc_traffic(kname, args.games, True)
+    if args.workload == "all" and args.model == "resnet" and args.nn_dtype == "fp32":
+        # the same self-play with the leaf net at the reference's own precision: every product
+        # on the exact-f32 MFMA (BK_NET_MATH=f32), timed the same way
+        from blokus_rl_amd.nets import net_math
+
+        if net_math() == "x3":
+            os.environ["BK_NET_MATH"] = "f32"
+            try:
+                _, _, fsims, fdt, _, _ = run_selfplay("resnet", "fp32", args.games, args.sims, args.steps,
+                                                      args.warmup, rank, args.node_cap, world, timers=False)
+            finally:
+                del os.environ["BK_NET_MATH"]
+            out["net_math_f32"] = {"value": _sum_over_ranks(fsims, world) / _max_over_ranks(fdt, world),
+                                   "unit": "sims/s", "dtype": "fp32 net: exact f32 MFMA products "
+                                   "(v_mfma_f32_16x16x4_f32, Winograd F(2x2,3x3) tower), BK_NET_MATH=f32"}
+    if args.workload == "all":
+        # env + search alone: the uninformed-MCTS opponent (DumbNet, compare_arena.py:87-95)
+        _, _, dsims, dt, dctr, dms = run_selfplay("dumbnet", "fp32", args.games, args.sims, args.steps,
+                                                  args.warmup, rank, args.node_cap, world)
+        dsims_all = _sum_over_ranks(dsims, world)
+        out["uninformed_mcts"] = {"value": dsims_all / _max_over_ranks(dt, world), "unit": "sims/s",
+                                  "stage_ms_per_sim_step": dms, "engine_counters": dctr}
+        largs = argparse.Namespace(**vars(args))
+        largs.steps, largs.warmup, largs.no_cpu_baseline = args.legal_steps, args.legal_warmup, True
+        legal = bench_legal(largs, world, rank)
+        out["legal_move"] = {k: legal[k] for k in ("metric", "value", "unit", "ms_per_step", "steps", "roofline")}
+        vargs = argparse.Namespace(**vars(args))
+        vargs.no_cpu_baseline = True
+        out["ppo_vector_env"] = bench_vecenv(vargs, world, rank)
+        out["learner"] = bench_train(args, world, rank)
+        if world == 1:
+            out["config1_7x7"] = bench_config1(args, args.cpu_pool, args.cpu_workers)
+            out["ppo_update"] = ppo_update_subprocess(args)
+    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+        pool, nw = args.cpu_pool, args.cpu_workers
+        out["cpu_baseline"] = cpu_baseline_selfplay(args.cpu_seconds, args.model, pool, nw)
+        if args.workload == "all":
+            out["cpu_baseline_uninformed"] = cpu_baseline_selfplay(args.cpu_seconds / 2, "dumbnet", pool, nw)
+            out["legal_move"]["cpu_baseline"] = cpu_baseline_legal(legal["_states"], args.cpu_seconds / 2, pool, nw)
+            out["ppo_vector_env"]["cpu_baseline"] = cpu_baseline_vecenv(args.cpu_seconds / 2, pool, nw)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=25)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: the self-play line's stage times, rooflines and "
+                         "late game, the other workloads' legs of --workload all (exact-f32 net, uninformed MCTS, "
+                         "legal moves, vector env, learner, 7x7 config 1, PPO updates) and the CPU baselines of "
+                         "any workload. Without it the run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy "
+                         "(float32; workloads all / selfplay / legal; rank 0's shard)")
     ap.add_argument("--workload", choices=["all", "legal", "selfplay", "vecenv", "train", "ppo", "dry"],
                     default="all")
     ap.add_argument("--ppo-updates", type=int, default=2)
@@ -966,10 +1077,14 @@ def main():
     ap.add_argument("--node-cap", type=int, default=None,
                     help="nodes per tree (default: sims x the longest game + 1, SelfPlay.node_cap_for)")
     args = ap.parse_args()
+    if args.dump_outputs and args.workload not in ("all", "selfplay", "legal"):
+        ap.error("--dump-outputs covers the workloads all, selfplay and legal")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # one process started with --gpus N: become the launcher of N ranks (nothing here has
         # touched the GPU; the ranks are child processes, not an exec of this one)
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
+    if not args.full:
+        args.no_cpu_baseline = True  # the CPU baselines are --full's
     args.cpu_workers, args.cpu_pool = 1, None
     if (not args.no_cpu_baseline and int(os.environ.get("WORLD_SIZE", "1")) == 1 and args.workload != "dry"
             and args.workload not in ("train", "ppo")):
@@ -996,75 +1111,17 @@ def main():
     elif args.workload == "ppo":
         out = bench_ppo(args, world, rank)
     else:
-        from blokus_rl_amd.alphazero.selfplay_bench import bench_selfplay, run_selfplay
-        out = bench_selfplay(args, world, rank)
-        sr = out.get("search_roofline", {})
-        if "k_leaf_step" in sr.get("kernel", ""):
-            # the leaf step's time over the timed window: the average over the window's launches in
-            # the committed kernel trace of this same command (profiles/r06_window_trace.json,
-            # tools/window_avg.py), beside this run's live sample after the window; HBM-side bytes
-            # per launch from the committed PMC passes over the same window: the fraction of the
-            # HBM roofline it draws (committed profiles, named as such)
-            sr["k_leaf_step_us_live_after_window"] = sr.pop("k_leaf_step_us", None)
-            win = _window_trace("k_leaf_step_ov", args)
-            sr["k_leaf_step_us"] = win["window_avg_us"] if win else sr["k_leaf_step_us_live_after_window"]
-            sr["k_leaf_step_us_source"] = (f"kernel-trace average over the window's {win['window_dispatches']} "
-                                           f"launches, {win['source']}" if win else "live sample after the window")
-            tr, src = _pmc_traffic("k_leaf_step_ov", args.games, with_source=True)
-            sr["traffic"], sr["traffic_source"] = tr, src
-            if tr and sr.get("k_leaf_step_us"):
-                sr["achieved_est"] = tr / (sr["k_leaf_step_us"] * 1e-6) / 1e9
-                sr["frac_est"] = sr["achieved_est"] / sr["peak"]
-        tw = _window_trace("k_leafnet_x3", args)
-        if tw and "tower_roofline" in out:
-            out["tower_roofline"]["kernel_ms_window_trace"] = tw["window_avg_us"] / 1e3
-            out["tower_roofline"]["kernel_ms_window_trace_source"] = tw["source"]
-        kname = out["roofline"].get("kernel", "").split(" ")[0]
-        if kname.startswith("k_conv3x3") or kname.startswith("k_tower") or kname.startswith("k_leafnet"):
-            # HBM bytes per launch from the committed PMC passes (profiles/r01_pmc_conv*.json)
-            out["roofline"]["traffic"], out["roofline"]["traffic_source"] = _pmc_traffic(kname, args.games, True)
-        if args.workload == "all" and args.model == "resnet" and args.nn_dtype == "fp32":
-            # the same self-play with the leaf net at the reference's own precision: every product
-            # on the exact-f32 MFMA (BK_NET_MATH=f32), timed the same way
-            from blokus_rl_amd.nets import net_math
+        from blokus_rl_amd.alphazero.selfplay_bench import bench_selfplay
 
-            if net_math() == "x3":
-                os.environ["BK_NET_MATH"] = "f32"
-                try:
-                    _, _, fsims, fdt, _, _ = run_selfplay("resnet", "fp32", args.games, args.sims, args.steps,
-                                                          args.warmup, rank, args.node_cap, world, timers=False)
-                finally:
-                    del os.environ["BK_NET_MATH"]
-                out["net_math_f32"] = {"value": _sum_over_ranks(fsims, world) / _max_over_ranks(fdt, world),
-                                       "unit": "sims/s", "dtype": "fp32 net: exact f32 MFMA products "
-                                       "(v_mfma_f32_16x16x4_f32, Winograd F(2x2,3x3) tower), BK_NET_MATH=f32"}
-        if args.workload == "all":
-            # env + search alone: the uninformed-MCTS opponent (DumbNet, compare_arena.py:87-95)
-            _, _, dsims, dt, dctr, dms = run_selfplay("dumbnet", "fp32", args.games, args.sims, args.steps,
-                                                      args.warmup, rank, args.node_cap, world)
-            dsims_all = _sum_over_ranks(dsims, world)
-            out["uninformed_mcts"] = {"value": dsims_all / _max_over_ranks(dt, world), "unit": "sims/s",
-                                      "stage_ms_per_sim_step": dms, "engine_counters": dctr}
-            largs = argparse.Namespace(**vars(args))
-            largs.steps, largs.warmup, largs.no_cpu_baseline = args.legal_steps, args.legal_warmup, True
-            legal = bench_legal(largs, world, rank)
-            out["legal_move"] = {k: legal[k] for k in ("metric", "value", "unit", "ms_per_step", "steps", "roofline")}
-            vargs = argparse.Namespace(**vars(args))
-            vargs.no_cpu_baseline = True
-            out["ppo_vector_env"] = bench_vecenv(vargs, world, rank)
-            out["learner"] = bench_train(args, world, rank)
-            if world == 1:
-                out["config1_7x7"] = bench_config1(args, args.cpu_pool, args.cpu_workers)
-                out["ppo_update"] = ppo_update_subprocess(args)
-        if rank == 0 and world == 1 and not args.no_cpu_baseline:
-            pool, nw = args.cpu_pool, args.cpu_workers
-            out["cpu_baseline"] = cpu_baseline_selfplay(args.cpu_seconds, args.model, pool, nw)
-            if args.workload == "all":
-                out["cpu_baseline_uninformed"] = cpu_baseline_selfplay(args.cpu_seconds / 2, "dumbnet", pool, nw)
-                out["legal_move"]["cpu_baseline"] = cpu_baseline_legal(legal["_states"], args.cpu_seconds / 2, pool, nw)
-                out["ppo_vector_env"]["cpu_baseline"] = cpu_baseline_vecenv(args.cpu_seconds / 2, pool, nw)
+        last = {} if args.dump_outputs else None
+        out = bench_selfplay(args, world, rank, last=last)
+        out["_outputs"] = last
+        if args.full:
+            selfplay_full_legs(out, args, world, rank)
     out.pop("_states", None)
-    pool = largs = vargs = None  # (the Namespace copies hold the pool too)
+    outputs = out.pop("_outputs", None)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, outputs)
     stop_cpu_pool(args)
     if dist_active():
         out["dist_backend"] = dist.get_backend()

@@ -87,7 +87,9 @@ def time_leaf_step(sp, n: int = 10):
 
 
 def run_selfplay(model_type: str, nn_dtype: str, G: int, sims: int, steps: int, warmup: int, rank: int,
-                 node_cap: int, world: int, timers: bool = True):
+                 node_cap: int, world: int, timers: bool = True, last: dict | None = None):
+    """`warmup` plies, then `steps` timed plies of G games. last: a dict that receives what the last
+    timed ply handed its caller (last_ply_outputs), taken before anything else advances the games."""
     torch.manual_seed(0)
     eng = Engine(20, 4, 5)
     model = build_model(model_type, 20, 4, eng.A, num_res_blocks=5).to(eng.device).eval()
@@ -121,6 +123,8 @@ def run_selfplay(model_type: str, nn_dtype: str, G: int, sims: int, steps: int, 
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if last is not None and steps > 0:
+        last.update(last_ply_outputs(sp))
     c1 = sp.check()  # raises on a node/child-table overflow or a root above cap
     done = sp.stats.sims - sims0
     delta = {k: c1[k] - c0[k] for k in c1 if k not in ("errors", "nodes", "children")}
@@ -128,6 +132,18 @@ def run_selfplay(model_type: str, nn_dtype: str, G: int, sims: int, steps: int, 
     if gather:
         ms["all_gather"] = gather
     return sp, eng, done, elapsed, delta, ms
+
+
+def last_ply_outputs(sp) -> dict:
+    """What the last play_ply() gave its caller, as device tensors (none is written in place by later
+    plies): the ply's record (root states, the legal ids and pi of each root, their count, the player
+    to move, the game id, whether the game moved), the sampled actions and the next root states. ids
+    and pi past a root's count are storage the ply leaves unwritten: -1 / 0 here."""
+    roots, ids, pi, k, player, gid, acted = sp._window[-1]
+    valid = torch.arange(ids.shape[1], device=ids.device).unsqueeze(0) < k.clamp(min=0).unsqueeze(1)
+    return {"roots": roots, "ids": torch.where(valid, ids, torch.full_like(ids, -1)),
+            "pi": torch.where(valid, pi, torch.zeros_like(pi)), "k": k, "player": player, "game_id": gid,
+            "acted": acted, "action": sp.last_action, "next_roots": sp.roots}
 
 
 def late_game(sp, plies: int, done: int) -> dict:
@@ -251,10 +267,14 @@ def net_dtype(args) -> str:
     return f"{args.nn_dtype} net / f64 search / u32 bitboards"
 
 
-def bench_selfplay(args, world, rank):
+def bench_selfplay(args, world, rank, last: dict | None = None):
+    """The self-play line. Without args.full only the timed window is run (the headline fields, the
+    window's engine counters and, over several ranks, its all-gather); args.full adds what takes runs
+    of its own: the stage-timed ply, the live kernel timings behind the rooflines, the late game."""
     G = args.games
+    full = bool(args.full)
     sp, eng, sims, elapsed, delta, ms = run_selfplay(args.model, args.nn_dtype, G, args.sims, args.steps,
-                                                     args.warmup, rank, args.node_cap, world)
+                                                     args.warmup, rank, args.node_cap, world, timers=full, last=last)
     local_sims = sims
     if dist_active():
         t = torch.tensor([elapsed, float(sims)], dtype=torch.float64, device="cuda")
@@ -262,7 +282,26 @@ def bench_selfplay(args, world, rank):
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dist.all_reduce(t)
         elapsed, sims = float(tmax[0].item()), int(t[1].item())
-    steps_sim = args.steps * args.sims  # sim-steps timed (one simulation per tree each)
+    head = {
+        "metric": "MCTS sims/sec on 20x20 Blokus (4 players, 256 games/GPU, 100 sims/move)",
+        "value": sims / elapsed,
+        "unit": "sims/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": net_dtype(args),
+        "data": "synthetic: continuous self-play from the empty board, random-init ResNet weights (seed 0)",
+        "config": {"workload": "config 3 (N=1) / 4 (N=8): AlphaZero self-play 20x20, 256 concurrent games per GPU, "
+                               "100 sims/move, ResNet-5x64 leaf eval", "global_batch": G * world,
+                   "parallelism": f"dp{world} (independent games)", "model": args.model},
+    }
+    if not full:
+        return dict(head, stage_ms_per_sim_step=ms, engine_counters=delta)
+    steps_sim =args.steps * args.sims  # sim-steps timed (one simulation per tree each)
     obs_bytes = 4 * 2 * eng.P * eng.N * eng.N
     conv = time_leaf_conv(sp) if args.nn_dtype == "fp32" else None
     ls = time_leaf_step(sp)
@@ -292,26 +331,7 @@ def bench_selfplay(args, world, rank):
                   "achieved": achieved / 1e9, "peak": HBM_PEAK / 1e9, "unit": "GB/s", "frac": achieved / HBM_PEAK,
                   "traffic": None, "bytes_per_sim_step": sbytes / steps_sim, "search_ms_per_sim_step": search_ms}
     late = late_game(sp, getattr(args, "late_plies", 0), args.warmup + args.steps + 1)
-    out = {
-        "metric": "MCTS sims/sec on 20x20 Blokus (4 players, 256 games/GPU, 100 sims/move)",
-        "value": sims / elapsed,
-        "unit": "sims/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": elapsed / args.steps * 1e3,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": net_dtype(args),
-        "data": "synthetic: continuous self-play from the empty board, random-init ResNet weights (seed 0)",
-        "config": {"workload": "config 3 (N=1) / 4 (N=8): AlphaZero self-play 20x20, 256 concurrent games per GPU, "
-                               "100 sims/move, ResNet-5x64 leaf eval", "global_batch": G * world,
-                   "parallelism": f"dp{world} (independent games)", "model": args.model},
-        "search_roofline": search,
-        "stage_ms_per_sim_step": ms,
-        "engine_counters": delta,
-    }
+    out = dict(head, search_roofline=search, stage_ms_per_sim_step=ms, engine_counters=delta)
     if late:
         out["late_game"] = late
     if conv is not None:

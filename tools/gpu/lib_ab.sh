@@ -5,7 +5,7 @@ cd "$GRAFT_REPO_ROOT" || exit 1
 mkdir -p gpurun_out
 for r in $(seq 1 ${ROUNDS:-2}); do
   for lib in "$@"; do
-    BK_LIB=$lib timeout -k 10 200 python bench.py --workload selfplay --steps ${STEPS:-6} --warmup ${WARMUP:-2} --late-plies 0 --no-cpu-baseline \
+    BK_LIB=$lib timeout -k 10 200 python bench.py --workload selfplay --full --steps ${STEPS:-6} --warmup ${WARMUP:-2} --late-plies 0 --no-cpu-baseline \
       > gpurun_out/ab.json 2> gpurun_out/ab.err || { echo "failed: $lib"; tail -5 gpurun_out/ab.err; exit 1; }
     python -c "import json,sys; d=json.load(open('gpurun_out/ab.json')); print('lib [%s]' % sys.argv[1], round(d['value']), 'step_us', round(d['search_roofline']['k_leaf_step_us'],1))" "$lib"
   done
