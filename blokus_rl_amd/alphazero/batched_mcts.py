@@ -15,6 +15,9 @@ import torch
 from ..engine import Engine, EngineError, _check, _ptr
 
 
+_OWN_OBS = object()  # leaf_step(obs=...): the default, BatchedMCTS.obs
+
+
 class BatchedMCTS:
     def __init__(self, eng: Engine, trees: int, node_cap: int = 8192, child_cap: int | None = None):
         self.eng = eng
@@ -78,23 +81,38 @@ class BatchedMCTS:
 
     def leaf_step(self, feat: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, values: torch.Tensor,
                   roots: torch.Tensor | None = None, active: torch.Tensor | None = None, cpuct: float = 1.0,
-                  want_mask: bool = True):
+                  want_mask: bool = True, obs=_OWN_OBS):
         """leaf_logits(feat, weight, bias) + expand_backup(None, values, 2) and, when roots is given,
         the next select(roots, active, cpuct) in one launch (bk_mcts_leaf_step; the same trees
         bitwise). Returns select's (status, obs, mask) or None. want_mask=False: the next leaves'
         bitmasks are not copied out (the engine keeps its own for the next step; self-play's
-        captured graph reads only status and obs), and the returned mask is stale."""
+        captured graph reads only status and obs), and the returned mask is stale. obs: the buffer
+        the next leaves' observation planes go to (default: self.obs), or None to write none (a net
+        that reads leaf_states_ptr and status needs none); the returned obs is then None."""
         assert feat.dtype == torch.float32 and feat.shape[0] == self.T and feat.stride(1) == 1
         assert weight.is_contiguous() and weight.shape == (self.eng.A, feat.shape[1]) and bias.shape == (self.eng.A,)
         assert values.dtype == torch.float32 and values.shape == (self.T, self.eng.P)
         sel = roots is not None
+        if obs is _OWN_OBS:
+            obs = self.obs
+        if obs is not None:
+            assert obs.dtype == torch.float32 and obs.shape == self.obs.shape and obs.device == self.obs.device
         _check(self.lib.bk_mcts_leaf_step(self.h, ctypes.c_void_p(feat.data_ptr()), feat.stride(0), feat.shape[1],
                                           _ptr(weight), _ptr(bias), _ptr(values), int(sel), _ptr(roots),
                                           _ptr(active), float(cpuct), _ptr(self.status) if sel else None,
-                                          _ptr(self.obs) if sel else None,
+                                          _ptr(obs) if sel else None,
                                           _ptr(self.leaf_mask) if sel and want_mask else None,
                                           self._s()))
-        return (self.status, self.obs, self.leaf_mask) if sel else None
+        return (self.status, obs, self.leaf_mask) if sel else None
+
+    @property
+    def leaf_states_ptr(self) -> int:
+        """Device address of the search's own [T, 384] leaf-state buffer (bk_mcts_leaf_states): the
+        row of a tree whose status is 1 is its current leaf, other rows are stale. It does not move
+        while this object lives, so a captured graph can hold it (nets.leafnet_x3_states takes it)."""
+        p = ctypes.c_void_p()
+        _check(self.lib.bk_mcts_leaf_states(self.h, ctypes.byref(p)))
+        return int(p.value)
 
     def root_policy(self, roots: torch.Tensor, active: torch.Tensor | None, temperature: float, cap: int = 2048,
                     zero: bool = True):

@@ -118,6 +118,30 @@ class LeafEvaluator:
             self.static_lp, self.static_v = self._forward(self.static_obs)
         self.graph = g
 
+    @property
+    def takes_states(self) -> bool:
+        """Whether forward_states runs the packed-state leaf kernel (bk_leafnet_x3_states): the sparse
+        HIP ResNet in fp32 with x3 math at a board size the kernel covers. Otherwise forward_states
+        observes the states and runs the planar forward."""
+        return bool(self.sparse and self.dtype == torch.float32 and self.model.takes_states())
+
+    def forward_states(self, states, status: torch.Tensor | None = None):
+        """The leaf batch from packed states [G, 384] uint8 instead of their observation planes: the
+        same outputs as __call__(eng.observe(states)) as float values. status [G] int32 (the search's
+        leaf status) or None: rows whose status is not 1 count as the all-zero observation, which is
+        what the search writes for them. With takes_states, states may be the device address of the
+        search's own buffer (BatchedMCTS.leaf_states_ptr; status then gives G)."""
+        if self.model is None:
+            return self.const_logp, self.const_v
+        if self.takes_states:
+            with torch.inference_mode():
+                lp, v = self.model.forward_states(states, status)
+                return lp.float().contiguous(), v.float().contiguous()
+        obs = self.eng.observe(states)
+        if status is not None:
+            obs = obs * (status == 1).view(-1, 1, 1, 1).to(obs.dtype)
+        return self._forward(obs)
+
     def __call__(self, obs: torch.Tensor):
         if self.model is None:
             return self.const_logp, self.const_v
@@ -134,7 +158,8 @@ class SelfPlay:
                  cpuct: float = 1.0, temperature: float = 1.0, dirichlet_alpha: float = 1.0,
                  dirichlet_weight: float = 0.25, node_cap: int | None = None, child_cap: int | None = None,
                  cap: int = 2048, seed: int = 0, nn_dtype: torch.dtype = torch.float32, use_graph: bool = True,
-                 continuous: bool = False, sim_graph_sims: int | None = None, record_plies: int | None = None):
+                 continuous: bool = False, sim_graph_sims: int | None = None, record_plies: int | None = None,
+                 leaf_input: str | None = None):
         self.eng = eng
         self.G = games
         self.num_sims = num_sims
@@ -157,6 +182,14 @@ class SelfPlay:
         self.mcts = BatchedMCTS(eng, games, node_cap=node_cap, child_cap=child_cap)
         self.evaluator = LeafEvaluator(model, eng, games, nn_dtype, use_graph)
         self._use_graph = use_graph
+        # what the leaf net reads: "planes" (the f32 observation the search writes per leaf) or
+        # "states" (the search's packed leaf states and status: no observation is written inside the
+        # simulation loop; the same trees). BK_LEAF_INPUT is read here like the other BK_* knobs;
+        # "states" needs an evaluator that takes states and falls back to "planes" without one
+        mode = leaf_input if leaf_input is not None else os.environ.get("BK_LEAF_INPUT", "planes")
+        if mode not in ("planes", "states"):
+            raise ValueError(f"leaf_input / BK_LEAF_INPUT must be planes or states, got {mode!r}")
+        self.leaf_input = mode if mode == "planes" or self.evaluator.takes_states else "planes"
         if getattr(self.evaluator, "planar", False) and self.evaluator.graph is not None:
             self.mcts.obs = self.evaluator.static_obs  # k_select writes the net's input buffer directly
         dev = eng.device
@@ -230,8 +263,12 @@ class SelfPlay:
     # ------------------------------------------------------------------ one simulation
     def _evaluate(self, obs):
         """Net on the leaf batch, leaving the priors' inputs in the search state: dense logits,
-        or (HIP ResNet) policy features + the sparse policy head over the legal ids."""
-        out, v = self.evaluator(obs)
+        or (HIP ResNet) policy features + the sparse policy head over the legal ids. leaf_input
+        "states": the net reads the search's leaf states and status instead of obs."""
+        if self.leaf_input == "states":
+            out, v = self.evaluator.forward_states(self.mcts.leaf_states_ptr, self.mcts.status)
+        else:
+            out, v = self.evaluator(obs)
         if self.evaluator.sparse:
             self.mcts.leaf_logits(out, self.evaluator.policy_w, self.evaluator.policy_b)
             return None, v, 2
@@ -283,7 +320,10 @@ class SelfPlay:
         if ev.model is None:
             self.mcts.expand_backup(ev.const_logp, ev.const_v, prior_mode=0)
             return
-        out, v = ev._forward(obs)
+        if self.leaf_input == "states":
+            out, v = ev.forward_states(self.mcts.leaf_states_ptr, self.mcts.status)
+        else:
+            out, v = ev._forward(obs)
         if ev.sparse:
             self.mcts.leaf_logits(out, ev.policy_w, ev.policy_b)
             self.mcts.expand_backup(None, v, prior_mode=2)
@@ -294,7 +334,8 @@ class SelfPlay:
         """sim_graph_sims simulations captured once. With the sparse policy head the search half of
         a simulation and the next one's descent are one launch (bk_mcts_leaf_step): select, then
         sim_graph_sims x {net, leaf_step (+ select, except the last)} — the trees of the per-stage
-        launches, bitwise (tests/test_sims_gpu.py)."""
+        launches, bitwise (tests/test_sims_gpu.py). leaf_input "states": the net reads the search's
+        leaf states and status, and the leaf steps write no observation (obs=None)."""
         if self._graph is None:
             self._g_roots = self.roots.clone()
             self._g_active = self.active.clone()
@@ -303,11 +344,16 @@ class SelfPlay:
             with torch.cuda.graph(g):
                 if ev.model is not None and ev.sparse:
                     _, obs, _ = self.mcts.select(self._g_roots, self._g_active, self.cpuct)
+                    states = self.leaf_input == "states"
                     for i in range(self.sim_graph_sims):
-                        out, v = ev._forward(obs)
+                        if states:
+                            out, v = ev.forward_states(self.mcts.leaf_states_ptr, self.mcts.status)
+                        else:
+                            out, v = ev._forward(obs)
                         last = i == self.sim_graph_sims - 1
                         self.mcts.leaf_step(out, ev.policy_w, ev.policy_b, v, None if last else self._g_roots,
-                                            self._g_active, self.cpuct, want_mask=False)
+                                            self._g_active, self.cpuct, want_mask=False,
+                                            obs=None if states else obs)
                 else:
                     for _ in range(self.sim_graph_sims):
                         self._sim_body()

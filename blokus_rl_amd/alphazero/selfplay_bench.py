@@ -33,7 +33,7 @@ def search_bytes(c: dict, sims: int, obs_bytes: int, mask_bytes: int) -> float:
             + c["expanded"] * (384 + mask_bytes + obs_bytes + mask_bytes + 36) + c["leaf_children"] * 24)
 
 
-def leaf_step_bytes(c: dict, sims: int, N: int, P: int, W64: int, F: int) -> float:
+def leaf_step_bytes(c: dict, sims: int, N: int, P: int, W64: int, F: int, obs: bool = True) -> float:
     """Algorithmic bytes of a sim-step's search launches on the timed path (k_select once per ply,
     then k_leaf_step per simulation) from engine counters, as the kernels move them:
     per simulation the root state (384); per descended level one 64-entry table probe (1 KB), the
@@ -42,9 +42,10 @@ def leaf_step_bytes(c: dict, sims: int, N: int, P: int, W64: int, F: int) -> flo
     bitmask written and re-read (2 x 8 W64), the observation (4 x 2P N^2), the policy features
     (4 F) and the value (16); per legal id of an expanded leaf its policy-Linear row and bias
     (4 F + 4: the sparse head, rows shared between trees are counted per use) and the child
-    initialised (20)."""
+    initialised (20). obs=False (leaf_input "states"): no observation is written."""
+    obs_bytes = 4 * 2 * P * N * N if obs else 0
     return (sims * 384 + c["levels"] * (1024 + 12 + 24) + c["scanned"] * 20
-            + c["expanded"] * (1040 + 768 + 2 * 8 * W64 + 4 * 2 * P * N * N + 4 * F + 16)
+            + c["expanded"] * (1040 + 768 + 2 * 8 * W64 + obs_bytes + 4 * F + 16)
             + c["leaf_children"] * (4 * F + 4 + 20))
 
 
@@ -65,12 +66,14 @@ def time_leaf_step(sp, n: int = 10):
     _, obs, _ = sp.mcts.select(sp.roots, sp.active, sp.cpuct)
     e_sel[1].record(st)
     steps = []
+    states = sp.leaf_input == "states"  # the net reads the search's leaf states: no observation written
     for i in range(n):
-        out, v = ev(obs)
+        out, v = ev.forward_states(sp.mcts.leaf_states_ptr, sp.mcts.status) if states else ev(obs)
         a, b = E(), E()
         a.record(st)
         last = i == n - 1
-        sp.mcts.leaf_step(out, ev.policy_w, ev.policy_b, v, None if last else sp.roots, sp.active, sp.cpuct)
+        sp.mcts.leaf_step(out, ev.policy_w, ev.policy_b, v, None if last else sp.roots, sp.active, sp.cpuct,
+                          obs=None if states else obs)
         b.record(st)
         steps.append((a, b))
     torch.cuda.synchronize()
@@ -81,7 +84,7 @@ def time_leaf_step(sp, n: int = 10):
     eng = sp.eng
     F = ev.policy_w.shape[1]
     active = int(sp.active.sum())
-    nbytes = leaf_step_bytes(d, active * n, eng.N, eng.P, eng.W, F)
+    nbytes = leaf_step_bytes(d, active * n, eng.N, eng.P, eng.W, F, obs=not states)
     return {"ms_per_sim_step": (sel_ms + sum(step_ms)) / n, "bytes_per_sim_step": nbytes / n,
             "k_leaf_step_us": 1e3 * sum(step_ms) / n, "k_select_us": 1e3 * sel_ms, "counters": d}
 
@@ -294,6 +297,7 @@ def bench_selfplay(args, world, rank, last: dict | None = None):
         "scaling": "weak",
         "vs_baseline": None,
         "dtype": net_dtype(args),
+        "leaf_input": sp.leaf_input,  # what the leaf net reads: planes (default) or states (BK_LEAF_INPUT)
         "data": "synthetic: continuous self-play from the empty board, random-init ResNet weights (seed 0)",
         "config": {"workload": "config 3 (N=1) / 4 (N=8): AlphaZero self-play 20x20, 256 concurrent games per GPU, "
                                "100 sims/move, ResNet-5x64 leaf eval", "global_batch": G * world,
@@ -302,7 +306,7 @@ def bench_selfplay(args, world, rank, last: dict | None = None):
     if not full:
         return dict(head, stage_ms_per_sim_step=ms, engine_counters=delta)
     steps_sim =args.steps * args.sims  # sim-steps timed (one simulation per tree each)
-    obs_bytes = 4 * 2 * eng.P * eng.N * eng.N
+    obs_bytes = 4 * 2 * eng.P * eng.N * eng.N if sp.leaf_input == "planes" else 0
     conv = time_leaf_conv(sp) if args.nn_dtype == "fp32" else None
     ls = time_leaf_step(sp)
     if ls is not None:

@@ -27,6 +27,8 @@
 #include "../../include/blokus_engine.h"
 #include "ctx.h"
 
+#include <type_traits>
+
 // the MFMA accumulators in VGPRs: the epilogue's VALU reads them without 100 v_accvgpr_read per
 // layer (AGPRs: 159.7 vs 157.9 us a launch, self-play +0.9%, three interleaved rounds on one box;
 // x0 still waits in AGPRs)
@@ -46,8 +48,26 @@ constexpr bool kLnEpiWrite = BK_LN_EPIW != 0;
 #endif
 constexpr bool kLnInterleave = BK_LN_IL != 0;
 
-template <int N>
-__global__ __launch_bounds__(kLnThreads, 1) void k_leafnet_x3(const float* __restrict__ obs,
+// The kernel's input form: the planar observation [B][8][N][N] f32 (as k_observe / the search
+// write it), or (STATES) the packed states it is made from, [B][kStateWords] words, with the
+// search's leaf status per board (null: every board is a leaf).
+struct LnStates {
+  const uint32_t* states;
+  const int32_t* status;
+};
+constexpr int kLnP = kStemCinX3 / 2;        // players of the 8-plane observation
+constexpr int kLnRowWords = kLnP * kMaxN;   // a state's board rows: plane p, row r = word p * kMaxN + r
+
+// STATES: the stem input is built from the board's state words instead of read as floats. Every
+// plane of the observation is binary (k_observe, env.hip), so the scaled board is 2^ex where a bit
+// is set and 0 elsewhere, ex = scale_exp(1) (scale_exp(0) on an all-zero board), and its lo half
+// is identically zero: only the hi plane is built and the stem takes two products per chunk
+// (ln_chunk_hi). The accumulators, and so every output, equal the planar form's on
+// bk_observe(states) as float values. A board whose status is not 1 (no leaf for the net: its
+// state row is stale) is the all-zero observation, as the search writes it in the planar form;
+// its state words are not loaded.
+template <int N, typename In>  // In: const float* (planes) or LnStates
+__global__ __launch_bounds__(kLnThreads, 1) void k_leafnet_x3(In in,
                                                               const h16x8* __restrict__ wstem,
                                                               const float* __restrict__ sstem,
                                                               const float* __restrict__ bstem,
@@ -56,6 +76,7 @@ __global__ __launch_bounds__(kLnThreads, 1) void k_leafnet_x3(const float* __res
                                                               const float* __restrict__ bt,
                                                               const float* __restrict__ bounds, int nlayers,
                                                               LnHeads hd, float* __restrict__ xout) {
+  constexpr bool STATES = std::is_same<In, LnStates>::value;
   constexpr int NN = N * N, RS = ln_row(N), NG = ln_groups(N), PIX_IT = (NN + kLnThreads - 1) / kLnThreads;
   constexpr int PL = ln_plane(N);
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
@@ -72,19 +93,28 @@ __global__ __launch_bounds__(kLnThreads, 1) void k_leafnet_x3(const float* __res
   LNSTAMP(30, __builtin_amdgcn_s_memrealtime());
 
   // the observation loads first (their latency under the halo zeroing below)
-  const float* ob = obs + b * kStemCinX3 * NN;
-  float xin[PIX_IT][kStemCinX3];
+  float xin[STATES ? 1 : PIX_IT][kStemCinX3];
+  uint32_t sw = 0u;  // STATES: thread tid < kLnRowWords holds row word tid, thread kLnRowWords to_move
+  bool live = true;
+  if constexpr (STATES) {
+    static_assert(kLnRowWords < kLnThreads && N <= kMaxN, "k_leafnet_x3: one state word per thread");
+    live = !in.status || in.status[b] == 1;
+    if (live && tid <= kLnRowWords) sw = in.states[b * kStateWords + (tid < kLnRowWords ? tid : kWToMove)];
+  } else {
+    const float* __restrict__ ob = in + b * kStemCinX3 * NN;
 #pragma unroll
-  for (int it = 0; it < PIX_IT; ++it) {
-    const int p = tid + it * kLnThreads;
+    for (int it = 0; it < PIX_IT; ++it) {
+      const int p = tid + it * kLnThreads;
 #pragma unroll
-    for (int c = 0; c < kStemCinX3; ++c) xin[it][c] = p < NN ? ob[c * NN + p] : 0.0f;
+      for (int c = 0; c < kStemCinX3; ++c) xin[it][c] = p < NN ? ob[c * NN + p] : 0.0f;
+    }
   }
   // zero the halo of all 18 planes (rows 0 and N+1, columns 0 and N+1..RS-1; the only slots read
-  // that no layer writes: interiors are written before they are read)
+  // that no layer writes: interiors are written before they are read); STATES: 17, the stem
+  // input has no lo plane
   {
     constexpr int kHaloCols = RS - N, kHalo = 2 * RS + N * kHaloCols;
-    for (int i = tid; i < 18 * kHalo; i += kLnThreads) {
+    for (int i = tid; i < (STATES ? 17 : 18) * kHalo; i += kLnThreads) {
       const int plane = i / kHalo, k = i - plane * kHalo;
       int row, col;
       if (k < 2 * RS) {
@@ -143,24 +173,63 @@ __global__ __launch_bounds__(kLnThreads, 1) void k_leafnet_x3(const float* __res
   const f32x4 s_stem = *reinterpret_cast<const f32x4*>(sstem + oc), b_stem = *reinterpret_cast<const f32x4*>(bstem + oc);
 
   // ---- stem input: the planar observation [8][N][N] of the board, scaled by its maximum, split
-  float m = 0.0f;
+  float max_obs;
+  int ex;
+  if constexpr (STATES) {
+    // the board's row words (bits past the board dropped, as the observation drops them) and
+    // to_move staged in the unused lo plane's space; the board maximum is 1 iff any plane has a
+    // cell set: a row bit, or a to_move that names one of the kLnP mover planes
+    uint32_t* rows = reinterpret_cast<uint32_t*>(sin + PL);
+    bool any = false;
+    if (tid < kLnRowWords) {
+      const uint32_t bits = tid % kMaxN < N ? sw & ((1u << N) - 1u) : 0u;
+      rows[tid] = bits;
+      any = bits != 0u;
+    } else if (tid == kLnRowWords) {
+      const uint32_t tm = live ? sw : ~0u;  // no mover plane of a board that is not a leaf
+      rows[kLnRowWords] = tm;
+      any = tm < (uint32_t)kLnP;
+    }
+    max_obs = block_max(any ? 1.0f : 0.0f, red + 8, wave, l);  // the barrier: zeroing and rows before the writes
+    ex = scale_exp(max_obs);
+    // a set cell's hi half: f16(2^ex), what split2 gives the planar form's 1.0f * 2^ex
+    const unsigned one = __builtin_bit_cast(unsigned short, (_Float16)ldexpf(1.0f, ex));
+    const uint32_t tm = rows[kLnRowWords];
+    const unsigned m01 = ((tm == 0u ? 1u : 0u) | (tm == 1u ? 0x10000u : 0u)) * one;
+    const unsigned m23 = ((tm == 2u ? 1u : 0u) | (tm == 3u ? 0x10000u : 0u)) * one;
 #pragma unroll
-  for (int it = 0; it < PIX_IT; ++it)
+    for (int it = 0; it < PIX_IT; ++it) {
+      const int p = tid + it * kLnThreads;
+      if (p < NN) {
+        const int r = p / N, c = p % N;
+        unsigned bit[kLnP];
 #pragma unroll
-    for (int c = 0; c < kStemCinX3; ++c) m = fmaxf(m, fabsf(xin[it][c]));
-  const float max_obs = block_max(m, red + 8, wave, l);  // the barrier also orders the zeroing before the writes
-  int ex = scale_exp(max_obs);
+        for (int q = 0; q < kLnP; ++q) bit[q] = (rows[q * kMaxN + r] >> c) & 1u;
+        // channels 2q (low 16 bits), 2q + 1 (high) per word, as split2 packs them
+        const u32x4 hi{(bit[0] | (bit[1] << 16)) * one, (bit[2] | (bit[3] << 16)) * one, m01, m23};
+        *reinterpret_cast<u32x4*>(sin + ((r + 1) * RS + c + 1) * 16) = hi;
+      }
+    }
+  } else {
+    float m = 0.0f;
 #pragma unroll
-  for (int it = 0; it < PIX_IT; ++it) {
-    const int p = tid + it * kLnThreads;
-    if (p < NN) {
-      unsigned h[4], o[4];
+    for (int it = 0; it < PIX_IT; ++it)
 #pragma unroll
-      for (int q = 0; q < 4; ++q) split2(ldexpf(xin[it][2 * q], ex), ldexpf(xin[it][2 * q + 1], ex), h[q], o[q]);
-      const u32x4 hi{h[0], h[1], h[2], h[3]}, lo{o[0], o[1], o[2], o[3]};
-      unsigned char* dst = sin + ((p / N + 1) * RS + p % N + 1) * 16;
-      *reinterpret_cast<u32x4*>(dst) = hi;
-      *reinterpret_cast<u32x4*>(dst + PL) = lo;
+      for (int c = 0; c < kStemCinX3; ++c) m = fmaxf(m, fabsf(xin[it][c]));
+    max_obs = block_max(m, red + 8, wave, l);  // the barrier also orders the zeroing before the writes
+    ex = scale_exp(max_obs);
+#pragma unroll
+    for (int it = 0; it < PIX_IT; ++it) {
+      const int p = tid + it * kLnThreads;
+      if (p < NN) {
+        unsigned h[4], o[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) split2(ldexpf(xin[it][2 * q], ex), ldexpf(xin[it][2 * q + 1], ex), h[q], o[q]);
+        const u32x4 hi{h[0], h[1], h[2], h[3]}, lo{o[0], o[1], o[2], o[3]};
+        unsigned char* dst = sin + ((p / N + 1) * RS + p % N + 1) * 16;
+        *reinterpret_cast<u32x4*>(dst) = hi;
+        *reinterpret_cast<u32x4*>(dst + PL) = lo;
+      }
     }
   }
   __syncthreads();
@@ -174,13 +243,24 @@ __global__ __launch_bounds__(kLnThreads, 1) void k_leafnet_x3(const float* __res
       const int t = 4 * j + ks < 9 ? 4 * j + ks : 8;
       return ((t / 3 - 1) * RS + (t % 3 - 1)) * 16 + kBias - ks * 4 * PL;  // from ab: the stem grid has 2 planes
     };
-    ln_prime<NG, PL>(rb, sin, ab, toff(0));
+    if constexpr (STATES) {  // no lo plane: two products per chunk
+      ln_prime_hi<NG>(rb, sin, ab, toff(0));
 #pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      if (j == 0)
-        ln_chunk<NG, true, PL>(acc, wsa[0][0], wsa[0][1], sin, ab, toff(0), toff(1), rb);
-      else
-        ln_chunk<NG, false, PL>(acc, wsa[j][0], wsa[j][1], sin, ab, toff(j), toff(j < 2 ? j + 1 : j), rb);
+      for (int j = 0; j < 3; ++j) {
+        if (j == 0)
+          ln_chunk_hi<NG, true>(acc, wsa[0][0], wsa[0][1], sin, ab, toff(0), toff(1), rb);
+        else
+          ln_chunk_hi<NG, false>(acc, wsa[j][0], wsa[j][1], sin, ab, toff(j), toff(j < 2 ? j + 1 : j), rb);
+      }
+    } else {
+      ln_prime<NG, PL>(rb, sin, ab, toff(0));
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {
+        if (j == 0)
+          ln_chunk<NG, true, PL>(acc, wsa[0][0], wsa[0][1], sin, ab, toff(0), toff(1), rb);
+        else
+          ln_chunk<NG, false, PL>(acc, wsa[j][0], wsa[j][1], sin, ab, toff(j), toff(j < 2 ? j + 1 : j), rb);
+      }
     }
   }
   ln_mfma_drain(acc);
@@ -536,7 +616,7 @@ int bk_leafnet_x3(const float* obs, int B, int N, int cin, const void* wstem, co
              "bk_leafnet_x3: 16-byte aligned buffers");
   if (B == 0) return BK_OK;
   {
-    const void* fns[2] = {(const void*)k_leafnet_x3<14>, (const void*)k_leafnet_x3<20>};
+    const void* fns[2] = {(const void*)k_leafnet_x3<14, const float*>, (const void*)k_leafnet_x3<20, const float*>};
     if (set_max_dynamic_lds(fns, 2, ln_lds_bytes(20)) != BK_OK) return BK_EHIP;
   }
   const LnHeads h{wp, bp, wv, bv, w1t, b1, w2, b2, P, pf, vout};
@@ -544,12 +624,46 @@ int bk_leafnet_x3(const float* obs, int B, int N, int cin, const void* wstem, co
   const h16x8* ws = reinterpret_cast<const h16x8*>(wstem);
   const h16x8* wt = reinterpret_cast<const h16x8*>(wtower);
   if (N == 20)
-    hipLaunchKernelGGL(k_leafnet_x3<20>, dim3(B), dim3(kLnThreads), ln_lds_bytes(20), s, obs, ws, sstem, bstem, wt,
-                       stower, btower, bounds, nlayers, h, out);
+    hipLaunchKernelGGL((k_leafnet_x3<20, const float*>), dim3(B), dim3(kLnThreads), ln_lds_bytes(20), s, obs, ws, sstem,
+                       bstem, wt, stower, btower, bounds, nlayers, h, out);
   else
-    hipLaunchKernelGGL(k_leafnet_x3<14>, dim3(B), dim3(kLnThreads), ln_lds_bytes(14), s, obs, ws, sstem, bstem, wt,
-                       stower, btower, bounds, nlayers, h, out);
+    hipLaunchKernelGGL((k_leafnet_x3<14, const float*>), dim3(B), dim3(kLnThreads), ln_lds_bytes(14), s, obs, ws, sstem,
+                       bstem, wt, stower, btower, bounds, nlayers, h, out);
   return launch_check("k_leafnet_x3");
+}
+
+int bk_leafnet_x3_states(const void* states, const int32_t* status, int B, int N, int P, const void* wstem,
+                         const float* sstem, const float* bstem, int nlayers, const void* wtower,
+                         const float* stower, const float* btower, const float* bounds, const float* wp,
+                         const float* bp, const float* wv, const float* bv, const float* w1t, const float* b1,
+                         const float* w2, const float* b2, float* pf, float* vout, float* out, void* stream) {
+  BK_REQUIRE(states && wstem && sstem && bstem && wtower && stower && btower && bounds && B >= 0, "bad argument");
+  BK_REQUIRE(wp && bp && wv && bv && w1t && b1 && w2 && b2 && pf && vout, "bad argument");
+  BK_REQUIRE(P == kLnP, "bk_leafnet_x3_states: P must be 4 (the stem takes 8 observation planes)");
+  BK_REQUIRE(nlayers >= 1, "bk_leafnet_x3_states: at least one tower conv");
+  BK_REQUIRE(bk_leafnet_x3_supported(N), "bk_leafnet_x3_states: N must be 14 or 20");
+  BK_REQUIRE(((uintptr_t)states & 3u) == 0, "bk_leafnet_x3_states: states must be 4-byte aligned");
+  const auto a16 = [](const void* p) { return ((uintptr_t)p & 15u) == 0; };
+  BK_REQUIRE(a16(wstem) && a16(wtower) && a16(sstem) && a16(bstem) && a16(stower) && a16(btower) && a16(wp) &&
+                 a16(wv) && a16(out),
+             "bk_leafnet_x3_states: 16-byte aligned buffers");
+  if (B == 0) return BK_OK;
+  {
+    const void* fns[2] = {(const void*)k_leafnet_x3<14, LnStates>, (const void*)k_leafnet_x3<20, LnStates>};
+    if (set_max_dynamic_lds(fns, 2, ln_lds_bytes(20)) != BK_OK) return BK_EHIP;
+  }
+  const LnHeads h{wp, bp, wv, bv, w1t, b1, w2, b2, P, pf, vout};
+  hipStream_t s = (hipStream_t)stream;
+  const h16x8* ws = reinterpret_cast<const h16x8*>(wstem);
+  const h16x8* wt = reinterpret_cast<const h16x8*>(wtower);
+  const LnStates in{reinterpret_cast<const uint32_t*>(states), status};
+  if (N == 20)
+    hipLaunchKernelGGL((k_leafnet_x3<20, LnStates>), dim3(B), dim3(kLnThreads), ln_lds_bytes(20), s, in, ws, sstem, bstem,
+                       wt, stower, btower, bounds, nlayers, h, out);
+  else
+    hipLaunchKernelGGL((k_leafnet_x3<14, LnStates>), dim3(B), dim3(kLnThreads), ln_lds_bytes(14), s, in, ws, sstem, bstem,
+                       wt, stower, btower, bounds, nlayers, h, out);
+  return launch_check("k_leafnet_x3 (states)");
 }
 
 }  // extern "C"

@@ -273,6 +273,41 @@ __device__ __forceinline__ void ln_chunk(f32x4 (&acc)[NG], h16x8 ah, h16x8 al, c
   }
 }
 
+// ln_prime / ln_chunk for a grid whose lo halves are identically zero (the stem on a binary
+// board built from a packed state, k_leafnet_x3<N, true>): only the hi plane exists, it alone is
+// read (ring entries [g][0]), and each group takes two MFMAs, acc[g] += ah*bh + al*bh, in
+// ln_chunk's order. The product left out, ah*bl with bl = 0, is the last of ln_chunk's triple and
+// adds exactly +-0, so every accumulator equals ln_chunk's as a float value.
+template <int NG>
+__device__ __forceinline__ void ln_prime_hi(h16x8 (&rb)[kLnSlots][2], const unsigned char* grid, const int (&pb)[NG],
+                                            int coff) {
+#pragma unroll
+  for (int g = 0; g < kLnPf; ++g) rb[g][0] = *reinterpret_cast<const h16x8*>(grid + pb[g] + coff);
+}
+template <int NG, bool INIT>
+__device__ __forceinline__ void ln_chunk_hi(f32x4 (&acc)[NG], h16x8 ah, h16x8 al, const unsigned char* grid,
+                                            const int (&pb)[NG], int coff, int coff_next, h16x8 (&rb)[kLnSlots][2]) {
+  static_assert(NG % kLnSlots == 0, "ln_chunk_hi: the ring slot of a group must not depend on the chunk");
+#pragma unroll
+  for (int g = 0; g < NG; ++g) {
+    const int gp = g + kLnPf;
+    rb[gp % kLnSlots][0] = *reinterpret_cast<const h16x8*>(grid + (gp < NG ? pb[gp] + coff : pb[gp - NG] + coff_next));
+    const h16x8 bh = rb[g % kLnSlots][0];
+    if (INIT)
+      asm volatile(
+          "v_mfma_f32_16x16x32_f16 %0, %1, %2, 0\n\t"
+          "v_mfma_f32_16x16x32_f16 %0, %3, %2, %0"
+          : BK_ACC_W(acc[g])
+          : "v"(ah), "v"(bh), "v"(al));
+    else
+      asm volatile(
+          "v_mfma_f32_16x16x32_f16 %0, %1, %2, %0\n\t"
+          "v_mfma_f32_16x16x32_f16 %0, %3, %2, %0"
+          : BK_ACC_RW(acc[g])
+          : "v"(ah), "v"(bh), "v"(al));
+  }
+}
+
 // ln_chunk with each group's two B-fragment reads (kLnPf groups ahead) issued between its three
 // MFMAs in one asm block: wait (lgkmcnt(2 (kLnPf - 1)): the reads of the kLnPf - 1 blocks before
 // are the only ones still allowed in flight), MFMA, read hi, MFMA, read lo, MFMA — one instruction in each MFMA's

@@ -510,7 +510,9 @@ int bk_mcts_leaf_step(bk_mcts* m, const float* feat, int64_t ldf, int F, const f
                       int32_t* leaf_status, float* obs, uint64_t* leaf_mask, void* stream) {
   BK_REQUIRE(m && feat && W && bias && values && F > 0 && F <= kMaxFeat && ldf >= F, "bad argument");
   BK_REQUIRE(((uintptr_t)W & 15u) == 0 || (F & 3) != 0, "bk_mcts_leaf_step: W must be 16-byte aligned");
-  BK_REQUIRE(!do_select || (roots && leaf_status && obs), "bad argument: select outputs");
+  // obs may be null: the next leaves' observation rows are then not written (their states and
+  // statuses are; bk_leafnet_x3_states reads those)
+  BK_REQUIRE(!do_select || (roots && leaf_status), "bad argument: select outputs");
   const DevPreset& dp = m->ctx->dp;
   const char* ov = getenv("BK_STEP_OVERLAP");  // read per call (graph capture reads it once)
   const int overlap = ov ? atoi(ov) : 1;
@@ -567,6 +569,12 @@ int bk_mcts_leaf_info(bk_mcts* m, void* leaf_states, int32_t* depths, void* stre
   if (!rc) rc = hip_check(hipMemcpyAsync(depths, m->d.depth, (size_t)m->d.T * sizeof(int32_t),
                                          hipMemcpyDeviceToDevice, (hipStream_t)stream), "copy depths");
   return rc;
+}
+
+int bk_mcts_leaf_states(bk_mcts* m, const void** states) {
+  BK_REQUIRE(m && states, "bad argument");
+  *states = m->d.leaf_state;
+  return BK_OK;
 }
 
 int bk_mcts_counters(bk_mcts* m, int64_t* out, void* stream) {

@@ -54,6 +54,7 @@ _SIGS = {
     "bk_mcts_root_stats": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
     "bk_mcts_counters": (_i, [_vp, _vp, _vp]),
     "bk_mcts_leaf_info": (_i, [_vp, _vp, _vp, _vp]),
+    "bk_mcts_leaf_states": (_i, [_vp, ctypes.POINTER(_vp)]),
     "bk_ply_policy": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, ctypes.c_double, ctypes.c_double, ctypes.c_uint64,
                            ctypes.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "bk_ply_finish": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
@@ -101,6 +102,8 @@ _SIGS = {
     "bk_leafnet_x3_weight_bytes": (_i, [_i]),
     "bk_leafnet_x3_supported": (_i, [_i]),
     "bk_leafnet_x3": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp] + [_vp] * 8 + [_i, _vp, _vp, _vp, _vp]),
+    "bk_leafnet_x3_states": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp] + [_vp] * 8
+                             + [_vp, _vp, _vp, _vp]),
     "bk_leafnet_w3_weight_bytes": (_i, []),
     "bk_leafnet_w3_supported": (_i, [_i]),
     "bk_leafnet_w3": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp] + [_vp] * 8 + [_i, _vp, _vp, _vp, _vp, _vp]),

@@ -386,6 +386,59 @@ def leafnet_x3(obs: torch.Tensor, model: "LeafResNet", want_out: bool = False):
     return (pf, v, out) if want_out else (pf, v)
 
 
+def leafnet_x3_states(states, status: torch.Tensor | None, model: "LeafResNet", want_out: bool = False):
+    """bk_leafnet_x3_states: packed states [B, 384] uint8 (N = the model's board) -> leafnet_x3's
+    outputs on their observation planes, as float values, without the planes. status [B] int32
+    (the search's leaf status) or None: rows whose status is not 1 are evaluated as the all-zero
+    observation and their state bytes are not read. states may also be the device address (int)
+    of a [B, 384] buffer the caller keeps alive (BatchedMCTS.leaf_states_ptr), with B = len(status)."""
+    from .engine import STATE_BYTES, _check, _ptr, _stream, load_library
+
+    f = model.f
+    dev = model.x3_wstem.device
+    if isinstance(states, torch.Tensor):
+        assert states.dtype == torch.uint8 and states.dim() == 2 and states.shape[1] == STATE_BYTES
+        assert states.is_contiguous() and states.device == dev
+        B, sptr = states.shape[0], ctypes.c_void_p(states.data_ptr())
+    else:
+        assert status is not None, "a raw states pointer needs status for the batch size"
+        B, sptr = status.shape[0], ctypes.c_void_p(int(states))
+    if status is not None:
+        assert status.dtype == torch.int32 and status.shape == (B,) and status.is_contiguous() and status.device == dev
+    N = model.board_size
+    lib = load_library()
+    nl = 2 * len(f.blocks)
+    assert model.x3_wtower.numel() == nl * lib.bk_leafnet_x3_weight_bytes(64)
+    assert model.x3_wstem.numel() == lib.bk_leafnet_x3_weight_bytes(8)
+    P = f.value_fc2.out_features
+    pf = torch.empty((B, 2 * N * N), dtype=torch.float32, device=dev)
+    v = torch.empty((B, P), dtype=torch.float32, device=dev)
+    out = torch.empty((B, 64, N, N), dtype=torch.float32, device=dev,
+                      memory_format=torch.channels_last) if want_out else None
+    h = model.x3_heads
+    _check(lib.bk_leafnet_x3_states(
+        sptr, _ptr(status), B, N, f.stem.in_channels // 2, _ptr(model.x3_wstem), _ptr(model.x3_sstem), _ptr(h[0]), nl,
+        _ptr(model.x3_wtower), _ptr(model.x3_stower), _ptr(model.b_tower), _ptr(model.x3_bounds),
+        *[_ptr(t) for t in h[1:]], _ptr(pf), _ptr(v),
+        None if out is None else ctypes.c_void_p(out.data_ptr()), _stream(dev)))
+    return (pf, v, out) if want_out else (pf, v)
+
+
+_OBSERVERS: dict = {}
+
+
+def _observe_states(states: torch.Tensor, N: int, P: int) -> torch.Tensor:
+    """bk_observe on states [B, 384] uint8 -> planes [B, 2P, N, N] f32, through an engine context
+    kept per (N, P, device) (the planes do not depend on the piece set)."""
+    from .engine import Engine
+
+    key = (N, P, states.device)
+    eng = _OBSERVERS.get(key)
+    if eng is None:
+        eng = _OBSERVERS[key] = Engine(N, P, 5, device=states.device)
+    return eng.observe(states.contiguous())
+
+
 def leafnet_w3(obs: torch.Tensor, model: "LeafResNet", want_out: bool = False):
     """bk_leafnet_w3: leafnet_x3's network and outputs with the residual tower as Winograd
     F(2x2,3x3) convolutions on split-f16 products (20x20 boards)."""
@@ -571,6 +624,37 @@ class LeafResNet(nn.Module):
         """bk_leafnet_x3's head operands (stem bias, policy/value 1x1 convs, value MLP), on the
         module's current device."""
         return [getattr(self, f"x3_head{i}") for i in range(9)]
+
+    @property
+    def board_size(self) -> int:
+        """N of the net's N x N board (the value MLP reads one feature per cell)."""
+        import math
+
+        return math.isqrt(self.f.value_fc1.in_features)
+
+    def takes_states(self) -> bool:
+        """Whether forward_states runs bk_leafnet_x3_states (else it observes and calls forward)."""
+        from .engine import load_library
+
+        return bool(self.x3 and net_math() == "x3" and load_library().bk_leafnet_x3_supported(self.board_size))
+
+    @torch.no_grad()
+    def forward_states(self, states: torch.Tensor, status: torch.Tensor | None = None):
+        """forward on the observation planes of packed states [B, 384] uint8, without the planes
+        where bk_leafnet_x3_states applies (takes_states): the same tuple, equal as float values.
+        status [B] int32 or None: rows whose status is not 1 count as the all-zero observation
+        (the search's stale leaf rows)."""
+        f = self.f
+        if self.takes_states():
+            pf, v = leafnet_x3_states(states, status, self)
+            if self.features:
+                return pf, v
+            logits = f.policy_out(pf)
+            return (F.log_softmax(logits, dim=1) if self.normalize else logits), v
+        obs = _observe_states(states, self.board_size, f.value_fc2.out_features)
+        if status is not None:
+            obs = obs * (status == 1).view(-1, 1, 1, 1).to(obs.dtype)
+        return self.forward(obs)
 
     @torch.no_grad()
     def forward(self, x):

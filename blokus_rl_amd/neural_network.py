@@ -81,6 +81,22 @@ class BlokusNNetWrapper:
             lp, v = self._infer(obs)
         return lp.float().contiguous(), v.float().contiguous()
 
+    @torch.inference_mode()
+    def predict_states(self, states: torch.Tensor):
+        """predict_batch from packed states: states [G, 384] uint8 on the device -> (logp [G, A] f32,
+        v [G, P] f32), equal as float values to predict_batch(Engine.observe(states)). The HIP
+        ResNet reads the states directly (LeafResNet.forward_states: no observation planes); every
+        other net observes them first."""
+        from .nets import LeafResNet, _observe_states
+
+        if self._infer is None:
+            self._infer = inference_model(self.model).to(memory_format=torch.channels_last)
+        states = states.to(self.device).contiguous()
+        if isinstance(self._infer, LeafResNet):
+            lp, v = self._infer.forward_states(states)
+            return lp.float().contiguous(), v.float().contiguous()
+        return self.predict_batch(_observe_states(states, self.game.board_size, self.game.number_of_players))
+
     def get_valid_dist(self, mask, logits, log_softmax=False):
         """neural_network.py:159-173."""
         dist = F.log_softmax(torch.masked_select(logits, mask), dim=-1)

@@ -174,7 +174,9 @@ int bk_mcts_leaf_logits(bk_mcts* m, const float* feat, int64_t ldf, int F, const
  * values, 2) -> (do_select) bk_mcts_select(roots, active, cpuct, leaf_status, obs, leaf_mask),
  * the same trees bitwise, without the grid-wide step between the three. Replaces, inside the
  * simulation loop (trainer.py:104-105), the end of one MCTS.simulate (mcts.py:60-70, the priors
- * of predict, neural_network.py:92-110) and the descent of the next (mcts.py:37-50). */
+ * of predict, neural_network.py:92-110) and the descent of the next (mcts.py:37-50).
+ * obs may be NULL: the next leaves' observation rows are then not written; their states
+ * (bk_mcts_leaf_states) and leaf_status are, which is what bk_leafnet_x3_states reads. */
 int bk_mcts_leaf_step(bk_mcts* m, const float* feat, int64_t ldf, int F, const float* W, const float* bias,
                       const float* values, int do_select, const void* roots, const int32_t* active, double cpuct,
                       int32_t* leaf_status, float* obs, uint64_t* leaf_mask, void* stream);
@@ -191,6 +193,11 @@ int bk_mcts_root_stats(bk_mcts* m, const void* roots, const int32_t* active, int
 
 /* Leaf of the last select pass, per tree: leaf_states [T][384] (device), depths [T] int32. */
 int bk_mcts_leaf_info(bk_mcts* m, void* leaf_states, int32_t* depths, void* stream);
+
+/* The device pointer of the search's own [T][384] leaf-state buffer (the row of a tree whose
+ * last select pass gave status 1 is that leaf; other rows are stale). Stable for the life of m,
+ * so a captured graph can hold it. */
+int bk_mcts_leaf_states(bk_mcts* m, const void** states);
 
 /* Engine counters (host copy, synchronises the stream): out[0] nodes used (all trees),
  * out[1] children used, out[2] selection levels descended (cumulative), out[3] leaves
@@ -439,6 +446,19 @@ int bk_leafnet_x3(const float* obs, int B, int N, int cin, const void* wstem, co
                   int nlayers, const void* wtower, const float* stower, const float* btower, const float* bounds,
                   const float* wp, const float* bp, const float* wv, const float* bv, const float* w1t, const float* b1,
                   const float* w2, const float* b2, int P, float* pf, float* vout, float* out, void* stream);
+
+/* bk_leafnet_x3 straight from packed states: states [B][384 bytes] (4-byte aligned) instead of
+ * their observation planes, and the outputs of bk_leafnet_x3(bk_observe(states)) as float values
+ * (every plane is binary, so the stem input is built from the state's row words and to_move; the
+ * product with its all-zero lo half is left out and adds exactly +-0). status (may be NULL): [B]
+ * int32, the search's leaf status; a board whose status is not 1 is evaluated as the all-zero
+ * observation (what the search writes for it in the planar form) and its state bytes are not
+ * read. P = 4 (8 planes); the other operands as bk_leafnet_x3. */
+int bk_leafnet_x3_states(const void* states, const int32_t* status, int B, int N, int P, const void* wstem,
+                         const float* sstem, const float* bstem, int nlayers, const void* wtower,
+                         const float* stower, const float* btower, const float* bounds, const float* wp,
+                         const float* bp, const float* wv, const float* bv, const float* w1t, const float* b1,
+                         const float* w2, const float* b2, float* pf, float* vout, float* out, void* stream);
 
 /* The same network and outputs as bk_leafnet_x3 with the residual tower as Winograd F(2x2,3x3)
  * convolutions on the same split-f16 products (leafnet_w3.hip: 16 products per 2x2 output tile
