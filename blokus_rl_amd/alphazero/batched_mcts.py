@@ -105,6 +105,44 @@ class BatchedMCTS:
                                           self._s()))
         return (self.status, obs, self.leaf_mask) if sel else None
 
+    def select_range(self, t0: int, n: int, roots: torch.Tensor, active: torch.Tensor | None, cpuct: float = 1.0):
+        """select() on the trees [t0, t0 + n) only (bk_mcts_select_range); the buffers are the whole
+        batch's and rows outside the range keep their contents."""
+        _check(self.lib.bk_mcts_select_range(self.h, int(t0), int(n), _ptr(roots), _ptr(active), float(cpuct),
+                                             _ptr(self.status), _ptr(self.obs), _ptr(self.leaf_mask), self._s()))
+        return self.status, self.obs, self.leaf_mask
+
+    def leaf_step_range(self, t0: int, n: int, feat: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor,
+                        values: torch.Tensor, roots: torch.Tensor | None = None, active: torch.Tensor | None = None,
+                        cpuct: float = 1.0):
+        """leaf_step() on the trees [t0, t0 + n) only (bk_mcts_leaf_step_range): feat and values are
+        the whole batch's [T, ...] buffers, of which the range's rows are read."""
+        assert feat.dtype == torch.float32 and feat.shape[0] == self.T and feat.stride(1) == 1
+        assert weight.is_contiguous() and weight.shape == (self.eng.A, feat.shape[1]) and bias.shape == (self.eng.A,)
+        assert values.dtype == torch.float32 and values.shape == (self.T, self.eng.P)
+        sel = roots is not None
+        _check(self.lib.bk_mcts_leaf_step_range(self.h, int(t0), int(n), ctypes.c_void_p(feat.data_ptr()),
+                                                feat.stride(0), feat.shape[1], _ptr(weight), _ptr(bias), _ptr(values),
+                                                int(sel), _ptr(roots), _ptr(active), float(cpuct),
+                                                _ptr(self.status) if sel else None, _ptr(self.obs) if sel else None,
+                                                _ptr(self.leaf_mask) if sel else None, self._s()))
+        return (self.status, self.obs, self.leaf_mask) if sel else None
+
+    def sims_pipelined(self, net_args, n_sims: int, groups: int, weight: torch.Tensor, bias: torch.Tensor,
+                       roots: torch.Tensor, active: torch.Tensor | None, cpuct: float = 1.0,
+                       obs: torch.Tensor | None = None, ring: int = 1):
+        """n_sims simulations of every tree as `groups` staggered chains of select, n_sims x {leaf
+        net, leaf step} on contiguous tree ranges (bk_mcts_sims_pipelined): the trees of the same
+        launches on the whole batch, bitwise. net_args: nets.leafnet_x3_args (its status must be
+        self.status); obs: the planes buffer the search writes, None when the net reads states.
+        ring: the scheduling edges between the groups' steps (0 none, 1 every simulation, 2 the first
+        only). n_sims = 0 only creates the group streams (call it once before capturing)."""
+        assert weight.is_contiguous() and bias.shape == (self.eng.A,)
+        assert weight.shape == (self.eng.A, 2 * self.eng.N * self.eng.N)
+        _check(self.lib.bk_mcts_sims_pipelined(self.h, ctypes.byref(net_args), int(n_sims), int(groups), int(ring),
+                                               _ptr(weight), _ptr(bias), _ptr(roots), _ptr(active), float(cpuct),
+                                               _ptr(self.status), _ptr(obs), self._s()))
+
     @property
     def leaf_states_ptr(self) -> int:
         """Device address of the search's own [T, 384] leaf-state buffer (bk_mcts_leaf_states): the

@@ -159,7 +159,8 @@ class SelfPlay:
                  dirichlet_weight: float = 0.25, node_cap: int | None = None, child_cap: int | None = None,
                  cap: int = 2048, seed: int = 0, nn_dtype: torch.dtype = torch.float32, use_graph: bool = True,
                  continuous: bool = False, sim_graph_sims: int | None = None, record_plies: int | None = None,
-                 leaf_input: str | None = None):
+                 leaf_input: str | None = None, sim_groups: int | None = None, sim_ring: int | bool | None = None,
+                 sim_groups_min_games: int = 64):
         self.eng = eng
         self.G = games
         self.num_sims = num_sims
@@ -192,6 +193,24 @@ class SelfPlay:
         self.leaf_input = mode if mode == "planes" or self.evaluator.takes_states else "planes"
         if getattr(self.evaluator, "planar", False) and self.evaluator.graph is not None:
             self.mcts.obs = self.evaluator.static_obs  # k_select writes the net's input buffer directly
+        # the captured simulations as sim_groups staggered chains over contiguous tree ranges
+        # (bk_mcts_sims_pipelined: one range's leaf step runs while the others are inside the net;
+        # the same trees). BK_SIM_GROUPS / BK_SIM_RING are read here like the other BK_* knobs. One
+        # group below sim_groups_min_games games (nothing to overlap) or without the x3 leaf net.
+        # sim_ring: the scheduling edges between the groups' steps, 0 none, 1 every simulation, 2 the
+        # first simulation of a graph only; default 1 for two groups, 2 for four, where the full ring
+        # (four steps in a row per simulation) is as long as the period itself
+        k = int(sim_groups if sim_groups is not None else os.environ.get("BK_SIM_GROUPS", self.SIM_GROUPS_DEFAULT))
+        if k not in (1, 2, 4):
+            raise ValueError(f"sim_groups / BK_SIM_GROUPS must be 1, 2 or 4, got {k}")
+        ev = self.evaluator
+        pipelined = (ev.sparse and ev.dtype == torch.float32 and ev.model.takes_states()
+                     and games >= max(sim_groups_min_games, k))
+        self.sim_groups = k if pipelined else 1
+        ring = sim_ring if sim_ring is not None else os.environ.get("BK_SIM_RING")
+        self.sim_ring = int(ring) if ring is not None else (1 if self.sim_groups == 2 else 2)
+        if self.sim_ring not in (0, 1, 2):
+            raise ValueError(f"sim_ring / BK_SIM_RING must be 0, 1 or 2, got {self.sim_ring}")
         dev = eng.device
         self.gen = torch.Generator(device=dev)
         self.gen.manual_seed(seed)
@@ -213,12 +232,16 @@ class SelfPlay:
         self._records: list[tuple[torch.Tensor, ...]] = []  # per-ply records (z resolved lazily)
         self.timers = None
         self._graph = None  # the captured simulations (_sim_graph)
+        self._pipe_args = None  # bk_mcts_sims_pipelined's net operands (_pipelined)
         self._window: list[tuple[torch.Tensor, ...]] = []  # records since mark_window()
         self._dropped_plies = 0  # continuous mode: plies that fell out of the record ring
         # an active game whose root had more children than `cap` (k_root returns counts = -K):
         # latched on the device, raised by check() at the next host sync
         self._cap_overflow = torch.zeros((), dtype=torch.int32, device=dev)
         self.last_action = torch.full((games,), -1, dtype=torch.int32, device=dev)
+
+    # sim_groups without an argument or BK_SIM_GROUPS (measured, profiles/sim_groups_bench.json)
+    SIM_GROUPS_DEFAULT = 4
 
     @staticmethod
     def max_game_plies(eng: Engine) -> int:
@@ -282,6 +305,27 @@ class SelfPlay:
         logp, v, mode = self._evaluate(obs)
         self.mcts.expand_backup(logp, v, prior_mode=mode)
 
+    def _pipelined(self, n: int, roots: torch.Tensor, active: torch.Tensor, eager: bool = False):
+        """n simulations as sim_groups staggered chains (bk_mcts_sims_pipelined) on the current
+        stream; n = 0 only creates the group streams. eager (no capture): at most two groups, with
+        the ring on every simulation — four eagerly fed streams are bound by the host's launches
+        (0.76M against 1.37M sims/s with two and 1.09M with one, profiles/sim_groups_bench.json)."""
+        if self._pipe_args is None:
+            from ..nets import leafnet_x3_args
+
+            ev, m, N = self.evaluator, self.mcts, self.eng.N
+            states = self.leaf_input == "states"
+            pf = torch.empty((self.G, 2 * N * N), dtype=torch.float32, device=self.eng.device)
+            v = torch.empty((self.G, self.eng.P), dtype=torch.float32, device=self.eng.device)
+            args = leafnet_x3_args(ev.model, pf, v, obs=None if states else m.obs,
+                                   states=m.leaf_states_ptr if states else None, status=m.status if states else None)
+            self._pipe_args = (args, pf, v, None if states else m.obs)  # the struct's buffers, kept alive
+        args, _, _, obs = self._pipe_args
+        ev = self.evaluator
+        groups, ring = (min(self.sim_groups, 2), 1) if eager else (self.sim_groups, self.sim_ring)
+        self.mcts.sims_pipelined(args, n, groups, ev.policy_w, ev.policy_b, roots, active, self.cpuct, obs=obs,
+                                 ring=ring)
+
     # simulations per captured graph (the constructor's sim_graph_sims or BK_SIM_GRAPH_SIMS; a ply's
     # n simulations = n // k replays + eager rest). Default: the whole ply in one graph (one k_select
     # per ply instead of one per replay: +0.5% sims/s at 100 sims vs k = 10), see graph_sims_for
@@ -305,6 +349,10 @@ class SelfPlay:
             for _ in range(n // k):
                 g.replay()
             n -= (n // k) * k
+        elif n > 0 and self.sim_groups > 1 and self.timers is None:
+            # no graph (BK_SIM_GRAPH=0): the same chains enqueued eagerly on the group streams
+            self._pipelined(n, self.roots, self.active, eager=True)
+            n = 0
         for _ in range(n):
             self.simulate()
 
@@ -335,14 +383,20 @@ class SelfPlay:
         a simulation and the next one's descent are one launch (bk_mcts_leaf_step): select, then
         sim_graph_sims x {net, leaf_step (+ select, except the last)} — the trees of the per-stage
         launches, bitwise (tests/test_sims_gpu.py). leaf_input "states": the net reads the search's
-        leaf states and status, and the leaf steps write no observation (obs=None)."""
+        leaf states and status, and the leaf steps write no observation (obs=None). sim_groups > 1:
+        the same launches per contiguous range of trees, as that many parallel branches of the graph
+        (bk_mcts_sims_pipelined; tests/test_sims_pipelined_gpu.py)."""
         if self._graph is None:
             self._g_roots = self.roots.clone()
             self._g_active = self.active.clone()
             ev = self.evaluator
+            if self.sim_groups > 1:
+                self._pipelined(0, self._g_roots, self._g_active)  # the group streams, before the capture
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
-                if ev.model is not None and ev.sparse:
+                if self.sim_groups > 1:
+                    self._pipelined(self.sim_graph_sims, self._g_roots, self._g_active)
+                elif ev.model is not None and ev.sparse:
                     _, obs, _ = self.mcts.select(self._g_roots, self._g_active, self.cpuct)
                     states = self.leaf_input == "states"
                     for i in range(self.sim_graph_sims):

@@ -47,22 +47,23 @@ __global__ __launch_bounds__(256) void k_reset(DevMcts m, const int32_t* flags) 
   if (blockIdx.x == 0 && threadIdx.x == 0) { m.tree_nodes[t] = 0; m.tree_children[t] = 0; }
 }
 
-// grid T x 256 threads: wave 0 descends, then the 4 waves build the leaf's legal bitmask (the
+// grid n x 256 threads, tree t0 + blockIdx.x: wave 0 descends, then the 4 waves build the leaf's legal bitmask (the
 // orientations split over the waves) and write its observation rows
 constexpr int kSelectWaves = 4;
 __global__ __launch_bounds__(64 * kSelectWaves) void k_select(DevPreset dp, DevMcts m, const uint32_t* __restrict__ roots,
                                                               const int32_t* __restrict__ active, double cpuct,
                                                               int32_t* __restrict__ status_out, float* __restrict__ obs,
-                                                              uint64_t* __restrict__ mask_out, double root_eps) {
+                                                              uint64_t* __restrict__ mask_out, double root_eps, int t0) {
   extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
   __shared__ int status_sh;
+  const int t = t0 + blockIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   if (wave == 0) {
-    const int st = select_descend(dp, m, blockIdx.x, roots, active, cpuct, status_out, lds, 0, nullptr, root_eps);
+    const int st = select_descend(dp, m, t, roots, active, cpuct, status_out, lds, 0, nullptr, root_eps);
     if (lane_id() == 0) status_sh = st;
   }
   __syncthreads();
-  select_leaf<kSelectWaves>(dp, m, blockIdx.x, status_sh, obs, mask_out, lds, wave);
+  select_leaf<kSelectWaves>(dp, m, t, status_sh, obs, mask_out, lds, wave);
 }
 
 // grid (T, kLeafBlocks) x 256 threads: workgroup c takes share c of the tree's legal ids
@@ -103,10 +104,10 @@ __global__ __launch_bounds__(64 * kStepWaves) void k_leaf_step(DevPreset dp, Dev
                                                                  const int32_t* __restrict__ active, double cpuct,
                                                                  int32_t* __restrict__ status_out,
                                                                  float* __restrict__ obs,
-                                                                 uint64_t* __restrict__ mask_out) {
+                                                                 uint64_t* __restrict__ mask_out, int t0) {
   extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
   __shared__ int status_sh;
-  const int t = blockIdx.x;
+  const int t = t0 + blockIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
 #ifdef BK_STAMPS
 #define BK_STEP_STAMP(i) \
@@ -154,11 +155,11 @@ __global__ __launch_bounds__(64 * kStepWaves) void k_leaf_step_ov(DevPreset dp, 
                                                                     int32_t* __restrict__ status_out,
                                                                     float* __restrict__ obs,
                                                                     uint64_t* __restrict__ mask_out, int sel_off,
-                                                                    int skipz) {
+                                                                    int skipz, int t0) {
   extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
   __shared__ int status_sh, status0_sh;
   __shared__ StepExpand sx;
-  const int t = blockIdx.x;
+  const int t = t0 + blockIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
 #ifdef BK_STAMPS
   // diag: 0 start, 1 the new node's entry published (wave 1), 2 wave 0 backup done, 3 wave 0 descent done, 4 the last logit
@@ -467,6 +468,13 @@ int bk_mcts_create(bk_ctx* ctx, int trees, int node_cap, int64_t child_cap, bk_m
 int bk_mcts_destroy(bk_mcts* m) {
   if (!m) return BK_OK;
   for (void* p : m->allocs) (void)hipFree(p);
+  for (hipStream_t s : m->pipe_stream)
+    if (s) (void)hipStreamDestroy(s);
+  for (hipEvent_t e : m->pipe_step)
+    if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : m->pipe_join)
+    if (e) (void)hipEventDestroy(e);
+  if (m->pipe_fork) (void)hipEventDestroy(m->pipe_fork);
   delete m;
   return BK_OK;
 }
@@ -478,20 +486,34 @@ int bk_mcts_reset(bk_mcts* m, const int32_t* reset_flags, void* stream) {
   return launch_check("k_reset");
 }
 
+// k_select on trees [t0, t0 + n): every pointer is the whole-batch buffer
+static int select_launch(bk_mcts* m, int t0, int n, const void* roots, const int32_t* active, double cpuct,
+                         double root_eps, int32_t* leaf_status, float* obs, uint64_t* leaf_mask, void* stream) {
+  if (n == 0) return BK_OK;
+  const DevPreset& dp = m->ctx->dp;
+  const size_t lds = sizeof(uint32_t) * (size_t)(kStateWords + 2 * kMaxN + dp.W32pad);
+  hipLaunchKernelGGL(k_select, dim3(n), dim3(kWave * kSelectWaves), lds, (hipStream_t)stream, dp, m->d,
+                     (const uint32_t*)roots, active, cpuct, leaf_status, obs, leaf_mask, root_eps, t0);
+  return launch_check("k_select");
+}
+
 int bk_mcts_select_eps(bk_mcts* m, const void* roots, const int32_t* active, double cpuct, double root_eps,
                        int32_t* leaf_status, float* obs, uint64_t* leaf_mask, void* stream) {
   BK_REQUIRE(m && roots && leaf_status && obs, "bad argument");
   BK_REQUIRE(root_eps >= 0.0, "bk_mcts_select_eps: root_eps >= 0");
-  const DevPreset& dp = m->ctx->dp;
-  const size_t lds = sizeof(uint32_t) * (size_t)(kStateWords + 2 * kMaxN + dp.W32pad);
-  hipLaunchKernelGGL(k_select, dim3(m->d.T), dim3(kWave * kSelectWaves), lds, (hipStream_t)stream, dp, m->d,
-                     (const uint32_t*)roots, active, cpuct, leaf_status, obs, leaf_mask, root_eps);
-  return launch_check("k_select");
+  return select_launch(m, 0, m->d.T, roots, active, cpuct, root_eps, leaf_status, obs, leaf_mask, stream);
 }
 
 int bk_mcts_select(bk_mcts* m, const void* roots, const int32_t* active, double cpuct, int32_t* leaf_status,
                    float* obs, uint64_t* leaf_mask, void* stream) {
   return bk_mcts_select_eps(m, roots, active, cpuct, 1e-6, leaf_status, obs, leaf_mask, stream);
+}
+
+int bk_mcts_select_range(bk_mcts* m, int t0, int n, const void* roots, const int32_t* active, double cpuct,
+                         int32_t* leaf_status, float* obs, uint64_t* leaf_mask, void* stream) {
+  BK_REQUIRE(m && roots && leaf_status && obs, "bk_mcts_select_range: bad argument");
+  BK_REQUIRE(t0 >= 0 && n >= 0 && (int64_t)t0 + n <= m->d.T, "bk_mcts_select_range: need 0 <= t0, 0 <= n, t0 + n <= T");
+  return select_launch(m, t0, n, roots, active, cpuct, 1e-6, leaf_status, obs, leaf_mask, stream);
 }
 
 int bk_mcts_leaf_logits(bk_mcts* m, const float* feat, int64_t ldf, int F, const float* W, const float* bias,
@@ -505,14 +527,12 @@ int bk_mcts_leaf_logits(bk_mcts* m, const float* feat, int64_t ldf, int F, const
   return launch_check("k_leaf_logits");
 }
 
-int bk_mcts_leaf_step(bk_mcts* m, const float* feat, int64_t ldf, int F, const float* W, const float* bias,
-                      const float* values, int do_select, const void* roots, const int32_t* active, double cpuct,
-                      int32_t* leaf_status, float* obs, uint64_t* leaf_mask, void* stream) {
-  BK_REQUIRE(m && feat && W && bias && values && F > 0 && F <= kMaxFeat && ldf >= F, "bad argument");
-  BK_REQUIRE(((uintptr_t)W & 15u) == 0 || (F & 3) != 0, "bk_mcts_leaf_step: W must be 16-byte aligned");
-  // obs may be null: the next leaves' observation rows are then not written (their states and
-  // statuses are; bk_leafnet_x3_states reads those)
-  BK_REQUIRE(!do_select || (roots && leaf_status), "bad argument: select outputs");
+// the leaf step on trees [t0, t0 + n): every pointer is the whole-batch buffer
+static int leaf_step_launch(bk_mcts* m, int t0, int n, const float* feat, int64_t ldf, int F, const float* W,
+                            const float* bias, const float* values, int do_select, const void* roots,
+                            const int32_t* active, double cpuct, int32_t* leaf_status, float* obs,
+                            uint64_t* leaf_mask, void* stream) {
+  if (n == 0) return BK_OK;
   const DevPreset& dp = m->ctx->dp;
   const char* ov = getenv("BK_STEP_OVERLAP");  // read per call (graph capture reads it once)
   const int overlap = ov ? atoi(ov) : 1;
@@ -521,18 +541,139 @@ int bk_mcts_leaf_step(bk_mcts* m, const float* feat, int64_t ldf, int F, const f
     const size_t words = (size_t)sel_off + kStateWords + 2 * kMaxN + dp.W32pad;
     const char* sz = getenv("BK_LEAF_SKIP0");  // W float4s of all-zero features not loaded (0: load all)
     const int skipz = sz ? atoi(sz) : 1;
-    hipLaunchKernelGGL(k_leaf_step_ov, dim3(m->d.T), dim3(kWave * kStepWaves), sizeof(uint32_t) * words,
+    hipLaunchKernelGGL(k_leaf_step_ov, dim3(n), dim3(kWave * kStepWaves), sizeof(uint32_t) * words,
                        (hipStream_t)stream, dp, m->d, feat, ldf, F, W, bias, values, do_select,
-                       (const uint32_t*)roots, active, cpuct, leaf_status, obs, leaf_mask, sel_off, skipz);
+                       (const uint32_t*)roots, active, cpuct, leaf_status, obs, leaf_mask, sel_off, skipz, t0);
     return launch_check("k_leaf_step_ov");
   }
   size_t words = (size_t)dp.W32pad + kLeafCap + F;                               // leaf logits
   words = std::max(words, (size_t)dp.W32pad + kExpandLdsIds);                    // expand
   words = std::max(words, (size_t)(kStateWords + 2 * kMaxN + dp.W32pad));       // select
-  hipLaunchKernelGGL(k_leaf_step, dim3(m->d.T), dim3(kWave * kStepWaves), sizeof(uint32_t) * words,
+  hipLaunchKernelGGL(k_leaf_step, dim3(n), dim3(kWave * kStepWaves), sizeof(uint32_t) * words,
                      (hipStream_t)stream, dp, m->d, feat, ldf, F, W, bias, values, do_select,
-                     (const uint32_t*)roots, active, cpuct, leaf_status, obs, leaf_mask);
+                     (const uint32_t*)roots, active, cpuct, leaf_status, obs, leaf_mask, t0);
   return launch_check("k_leaf_step");
+}
+
+int bk_mcts_leaf_step(bk_mcts* m, const float* feat, int64_t ldf, int F, const float* W, const float* bias,
+                      const float* values, int do_select, const void* roots, const int32_t* active, double cpuct,
+                      int32_t* leaf_status, float* obs, uint64_t* leaf_mask, void* stream) {
+  BK_REQUIRE(m && feat && W && bias && values && F > 0 && F <= kMaxFeat && ldf >= F, "bad argument");
+  BK_REQUIRE(((uintptr_t)W & 15u) == 0 || (F & 3) != 0, "bk_mcts_leaf_step: W must be 16-byte aligned");
+  // obs may be null: the next leaves' observation rows are then not written (their states and
+  // statuses are; bk_leafnet_x3_states reads those)
+  BK_REQUIRE(!do_select || (roots && leaf_status), "bad argument: select outputs");
+  return leaf_step_launch(m, 0, m->d.T, feat, ldf, F, W, bias, values, do_select, roots, active, cpuct, leaf_status,
+                          obs, leaf_mask, stream);
+}
+
+int bk_mcts_leaf_step_range(bk_mcts* m, int t0, int n, const float* feat, int64_t ldf, int F, const float* W,
+                            const float* bias, const float* values, int do_select, const void* roots,
+                            const int32_t* active, double cpuct, int32_t* leaf_status, float* obs,
+                            uint64_t* leaf_mask, void* stream) {
+  BK_REQUIRE(m && feat && W && bias && values && F > 0 && F <= kMaxFeat && ldf >= F,
+             "bk_mcts_leaf_step_range: bad argument");
+  BK_REQUIRE(((uintptr_t)W & 15u) == 0 || (F & 3) != 0, "bk_mcts_leaf_step_range: W must be 16-byte aligned");
+  BK_REQUIRE(!do_select || (roots && leaf_status), "bk_mcts_leaf_step_range: bad argument: select outputs");
+  BK_REQUIRE(t0 >= 0 && n >= 0 && (int64_t)t0 + n <= m->d.T,
+             "bk_mcts_leaf_step_range: need 0 <= t0, 0 <= n, t0 + n <= T");
+  return leaf_step_launch(m, t0, n, feat, ldf, F, W, bias, values, do_select, roots, active, cpuct, leaf_status, obs,
+                          leaf_mask, stream);
+}
+
+// The streams and events of bk_mcts_sims_pipelined, once per object.
+static int pipe_prepare(bk_mcts* m) {
+  if (m->pipe_ready) return BK_OK;
+  int rc = hip_check(hipSetDevice(m->ctx->device), "hipSetDevice");
+  for (int g = 0; !rc && g < bk_mcts::kMaxGroups - 1; ++g) {
+    if (!m->pipe_stream[g])
+      rc = hip_check(hipStreamCreateWithFlags(&m->pipe_stream[g], hipStreamNonBlocking), "create group stream");
+    if (!rc && !m->pipe_join[g])
+      rc = hip_check(hipEventCreateWithFlags(&m->pipe_join[g], hipEventDisableTiming), "create join event");
+  }
+  for (int g = 0; !rc && g < bk_mcts::kMaxGroups; ++g)
+    if (!m->pipe_step[g])
+      rc = hip_check(hipEventCreateWithFlags(&m->pipe_step[g], hipEventDisableTiming), "create step event");
+  if (!rc && !m->pipe_fork) rc = hip_check(hipEventCreateWithFlags(&m->pipe_fork, hipEventDisableTiming), "create fork event");
+  if (!rc) m->pipe_ready = true;
+  return rc;
+}
+
+// the leaf net on trees [t0, t0 + n) of the whole-batch buffers in a: the public entries, on offset rows
+static int pipe_net(const bk_leafnet_args* a, int t0, int n, void* stream) {
+  const size_t F = (size_t)2 * a->N * a->N;
+  float* pf = a->pf + (size_t)t0 * F;
+  float* vout = a->vout + (size_t)t0 * a->P;
+  if (a->states)
+    return bk_leafnet_x3_states((const char*)a->states + (size_t)t0 * kStateBytes, a->status ? a->status + t0 : nullptr,
+                                n, a->N, a->P, a->wstem, a->sstem, a->bstem, a->nlayers, a->wtower, a->stower,
+                                a->btower, a->bounds, a->wp, a->bp, a->wv, a->bv, a->w1t, a->b1, a->w2, a->b2, pf,
+                                vout, nullptr, stream);
+  return bk_leafnet_x3(a->obs + (size_t)t0 * 2 * a->P * a->N * a->N, n, a->N, 2 * a->P, a->wstem, a->sstem, a->bstem,
+                       a->nlayers, a->wtower, a->stower, a->btower, a->bounds, a->wp, a->bp, a->wv, a->bv, a->w1t,
+                       a->b1, a->w2, a->b2, a->P, pf, vout, nullptr, stream);
+}
+
+int bk_mcts_sims_pipelined(bk_mcts* m, const bk_leafnet_args* net, int n_sims, int groups, int ring, const float* W,
+                           const float* bias, const void* roots, const int32_t* active, double cpuct,
+                           int32_t* leaf_status, float* obs, void* stream) {
+  BK_REQUIRE(m && net && W && bias && roots && leaf_status, "bk_mcts_sims_pipelined: bad argument");
+  BK_REQUIRE(groups == 1 || groups == 2 || groups == 4, "bk_mcts_sims_pipelined: groups must be 1, 2 or 4");
+  BK_REQUIRE(n_sims >= 0, "bk_mcts_sims_pipelined: n_sims >= 0");
+  BK_REQUIRE(ring >= 0 && ring <= 2, "bk_mcts_sims_pipelined: ring must be 0, 1 or 2");
+  BK_REQUIRE((net->obs != nullptr) != (net->states != nullptr),
+             "bk_mcts_sims_pipelined: the net reads either obs or states");
+  BK_REQUIRE(!net->obs || obs == net->obs, "bk_mcts_sims_pipelined: the search must write the planes the net reads");
+  BK_REQUIRE(!net->states || net->status == leaf_status,
+             "bk_mcts_sims_pipelined: the net must read the status the search writes");
+  BK_REQUIRE(net->pf && net->vout && net->P > 0 && net->P <= kMaxP && net->N > 0 && net->N <= kMaxN,
+             "bk_mcts_sims_pipelined: bad net arguments");
+  const int F = 2 * net->N * net->N;
+  BK_REQUIRE(F <= kMaxFeat, "bk_mcts_sims_pipelined: too many policy features");
+  BK_REQUIRE(((uintptr_t)W & 15u) == 0 || (F & 3) != 0, "bk_mcts_sims_pipelined: W must be 16-byte aligned");
+  int rc = pipe_prepare(m);
+  if (rc || n_sims == 0) return rc;
+  const int T = m->d.T;
+  const int per = (T + groups - 1) / groups;
+  const int G = (T + per - 1) / per;  // the non-empty groups: [g * per, min(T, (g + 1) * per))
+  hipStream_t st[bk_mcts::kMaxGroups];
+  st[0] = (hipStream_t)stream;
+  for (int g = 1; g < G; ++g) st[g] = m->pipe_stream[g - 1];
+  // fork: groups 1.. start after whatever the caller's stream holds
+  int forked = 1;
+  if (G > 1) rc = hip_check(hipEventRecord(m->pipe_fork, st[0]), "record fork");
+  for (int g = 1; !rc && g < G; ++g) {
+    rc = hip_check(hipStreamWaitEvent(st[g], m->pipe_fork, 0), "fork group stream");
+    if (!rc) forked = g + 1;
+  }
+  const auto n_of = [&](int g) { return std::min(T, (g + 1) * per) - g * per; };
+  for (int g = 0; !rc && g < G; ++g)
+    rc = select_launch(m, g * per, n_of(g), roots, active, cpuct, 1e-6, leaf_status, obs, nullptr, st[g]);
+  for (int g = 0; !rc && g < G; ++g) rc = pipe_net(net, g * per, n_of(g), st[g]);
+  // simulation-major, so a ring edge's event is always recorded before it is waited for. A step is
+  // followed at once by its own group's next net: under capture a node's first successor is then
+  // the next node of its own branch, and the ring edge to the next group's step comes second
+  for (int s = 0; !rc && s < n_sims; ++s) {
+    const int do_select = s + 1 < n_sims;
+    const bool edges = G > 1 && (ring == 1 || (ring == 2 && s == 0));
+    for (int g = 0; !rc && g < G; ++g) {
+      // scheduling only: step(g, s) after step(g - 1, s), step(0, s) after step(G - 1, s - 1)
+      if (edges && (g > 0 || s > 0))
+        rc = hip_check(hipStreamWaitEvent(st[g], m->pipe_step[g > 0 ? g - 1 : G - 1], 0), "ring edge");
+      if (!rc)
+        rc = leaf_step_launch(m, g * per, n_of(g), net->pf, F, F, W, bias, net->vout, do_select, roots, active, cpuct,
+                              leaf_status, obs, nullptr, st[g]);
+      if (!rc && edges) rc = hip_check(hipEventRecord(m->pipe_step[g], st[g]), "record step");
+      if (!rc && do_select) rc = pipe_net(net, g * per, n_of(g), st[g]);
+    }
+  }
+  // join every forked stream, also after a failure (a capture must not end with a branch open)
+  for (int g = 1; g < forked; ++g) {
+    int rj = hip_check(hipEventRecord(m->pipe_join[g - 1], st[g]), "record join");
+    if (!rj) rj = hip_check(hipStreamWaitEvent(st[0], m->pipe_join[g - 1], 0), "join group stream");
+    if (!rc) rc = rj;
+  }
+  return rc;
 }
 
 int bk_mcts_expand_backup(bk_mcts* m, const float* logp, const float* values, int prior_mode, void* stream) {

@@ -1107,4 +1107,10 @@ struct bk_mcts {
   bk_ctx* ctx = nullptr;
   bk::DevMcts d{};
   std::vector<void*> allocs;
+  // bk_mcts_sims_pipelined: the streams of tree groups 1.. and the events that fork them from,
+  // order them against and join them to the caller's stream (created at the first call)
+  static constexpr int kMaxGroups = 4;
+  bool pipe_ready = false;
+  hipStream_t pipe_stream[kMaxGroups - 1] = {};
+  hipEvent_t pipe_fork = nullptr, pipe_step[kMaxGroups] = {}, pipe_join[kMaxGroups - 1] = {};
 };

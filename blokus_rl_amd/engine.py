@@ -50,6 +50,10 @@ _SIGS = {
     "bk_mcts_leaf_logits": (_i, [_vp, _vp, ctypes.c_int64, _i, _vp, _vp, _vp]),
     "bk_mcts_leaf_step": (_i, [_vp, _vp, ctypes.c_int64, _i, _vp, _vp, _vp, _i, _vp, _vp, ctypes.c_double, _vp,
                                _vp, _vp, _vp]),
+    "bk_mcts_select_range": (_i, [_vp, _i, _i, _vp, _vp, ctypes.c_double, _vp, _vp, _vp, _vp]),
+    "bk_mcts_leaf_step_range": (_i, [_vp, _i, _i, _vp, ctypes.c_int64, _i, _vp, _vp, _vp, _i, _vp, _vp,
+                                     ctypes.c_double, _vp, _vp, _vp, _vp]),
+    "bk_mcts_sims_pipelined": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, ctypes.c_double, _vp, _vp, _vp]),
     "bk_mcts_root_policy": (_i, [_vp, _vp, _vp, ctypes.c_double, _vp, _vp, _i, _vp, _vp]),
     "bk_mcts_root_stats": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
     "bk_mcts_counters": (_i, [_vp, _vp, _vp]),
@@ -110,6 +114,13 @@ _SIGS = {
 }
 
 _LIB = None
+
+
+class LeafnetArgs(ctypes.Structure):
+    """bk_leafnet_args (include/blokus_engine.h): the leaf net's operands for bk_mcts_sims_pipelined."""
+    _fields_ = ([("obs", _vp), ("states", _vp), ("status", _vp), ("N", _i), ("P", _i), ("nlayers", _i)]
+                + [(k, _vp) for k in ("wstem", "sstem", "bstem", "wtower", "stower", "btower", "bounds", "wp", "bp",
+                                      "wv", "bv", "w1t", "b1", "w2", "b2", "pf", "vout")])
 
 
 class EngineError(RuntimeError):

@@ -424,6 +424,44 @@ def leafnet_x3_states(states, status: torch.Tensor | None, model: "LeafResNet", 
     return (pf, v, out) if want_out else (pf, v)
 
 
+def leafnet_x3_args(model: "LeafResNet", pf: torch.Tensor, v: torch.Tensor, obs: torch.Tensor | None = None,
+                    states=None, status: torch.Tensor | None = None):
+    """The operands of leafnet_x3(obs, model) or leafnet_x3_states(states, status, model) as one
+    bk_leafnet_args struct (engine.LeafnetArgs) for bk_mcts_sims_pipelined, with pf [B, 2*N*N] and
+    v [B, P] as the outputs. The struct holds raw addresses: the caller keeps model, obs / states,
+    status, pf and v alive while it is in use (a captured graph: as long as the graph)."""
+    from .engine import LeafnetArgs, load_library
+
+    assert (obs is None) != (states is None)
+    f = model.f
+    lib = load_library()
+    N, P, nl = model.board_size, f.value_fc2.out_features, 2 * len(f.blocks)
+    assert model.x3 and f.stem.in_channels == 2 * P and lib.bk_leafnet_x3_supported(N)
+    assert model.x3_wtower.numel() == nl * lib.bk_leafnet_x3_weight_bytes(64)
+    assert model.x3_wstem.numel() == lib.bk_leafnet_x3_weight_bytes(8)
+    B = pf.shape[0]
+    dev = model.x3_wstem.device
+    for t, shape in ((pf, (B, 2 * N * N)), (v, (B, P))):
+        assert t.dtype == torch.float32 and t.shape == shape and t.is_contiguous() and t.device == dev
+    a = LeafnetArgs()
+    if obs is not None:
+        assert obs.dtype == torch.float32 and obs.shape == (B, 2 * P, N, N) and obs.is_contiguous() and obs.device == dev
+        a.obs = obs.data_ptr()
+    else:
+        assert status is not None and status.dtype == torch.int32 and status.shape == (B,) and status.device == dev
+        a.states = states.data_ptr() if isinstance(states, torch.Tensor) else int(states)
+        a.status = status.data_ptr()
+    a.N, a.P, a.nlayers = N, P, nl
+    h = model.x3_heads
+    tensors = {"wstem": model.x3_wstem, "sstem": model.x3_sstem, "bstem": h[0], "wtower": model.x3_wtower,
+               "stower": model.x3_stower, "btower": model.b_tower, "bounds": model.x3_bounds, "pf": pf, "vout": v}
+    tensors.update(zip(("wp", "bp", "wv", "bv", "w1t", "b1", "w2", "b2"), h[1:]))
+    for k, t in tensors.items():
+        assert t.is_contiguous() and t.device == dev
+        setattr(a, k, t.data_ptr())
+    return a
+
+
 _OBSERVERS: dict = {}
 
 

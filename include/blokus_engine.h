@@ -181,6 +181,18 @@ int bk_mcts_leaf_step(bk_mcts* m, const float* feat, int64_t ldf, int F, const f
                       const float* values, int do_select, const void* roots, const int32_t* active, double cpuct,
                       int32_t* leaf_status, float* obs, uint64_t* leaf_mask, void* stream);
 
+/* bk_mcts_select / bk_mcts_leaf_step on the trees [t0, t0 + n) only (n workgroups). Every pointer
+ * is still the whole batch's buffer, indexed by absolute tree; trees outside the range are not
+ * touched. The whole-batch entries are the range [0, T). n = 0 launches nothing; t0 < 0, n < 0
+ * or t0 + n > T is BK_EINVAL. Trees are independent, so ranges that cover [0, T) once — in any
+ * order, on any streams — leave the trees of the whole-batch call, bitwise. */
+int bk_mcts_select_range(bk_mcts* m, int t0, int n, const void* roots, const int32_t* active, double cpuct,
+                         int32_t* leaf_status, float* obs, uint64_t* leaf_mask, void* stream);
+int bk_mcts_leaf_step_range(bk_mcts* m, int t0, int n, const float* feat, int64_t ldf, int F, const float* W,
+                            const float* bias, const float* values, int do_select, const void* roots,
+                            const int32_t* active, double cpuct, int32_t* leaf_status, float* obs,
+                            uint64_t* leaf_mask, void* stream);
+
 /* get_distribution (mcts.py:73-99) at the root of every active tree: ids[t][0..K) and
  * pi[t][0..K) (f64) in child order, K in counts[t]; temperature 0 -> one-hot argmax N
  * (first max); all-zero N -> uniform. Rows are `cap` wide. Root must be expanded. */
@@ -474,6 +486,56 @@ int bk_leafnet_w3(const float* obs, int B, int N, int cin, const void* wstem, co
                   const float* wp, const float* bp, const float* wv, const float* bv, const float* w1t, const float* b1,
                   const float* w2, const float* b2, int P, float* pf, float* vout, float* x0ws, float* out,
                   void* stream);
+
+/* ---------------------------------------------------------------- pipelined simulations
+ * The operands of bk_leafnet_x3 / bk_leafnet_x3_states as one struct, every buffer the whole
+ * batch's: exactly one of obs ([T][2P][N][N] f32, bk_leafnet_x3) and states ([T][384 bytes] with
+ * status [T], bk_leafnet_x3_states) is set; pf [T][2NN] and vout [T][P] are the outputs. */
+typedef struct bk_leafnet_args {
+  const float* obs;
+  const void* states;
+  const int32_t* status;
+  int N, P, nlayers;
+  const void* wstem;
+  const float* sstem;
+  const float* bstem;
+  const void* wtower;
+  const float* stower;
+  const float* btower;
+  const float* bounds;
+  const float* wp;
+  const float* bp;
+  const float* wv;
+  const float* bv;
+  const float* w1t;
+  const float* b1;
+  const float* w2;
+  const float* b2;
+  float* pf;
+  float* vout;
+} bk_leafnet_args;
+
+/* n_sims simulations of every tree, the trees split into `groups` (1, 2 or 4) contiguous ranges
+ * of ceil(T / groups) trees (empty ranges are skipped), each range a chain of its own:
+ *   select, then n_sims x { leaf net on the range's rows, leaf step on the range }
+ * (the last step without the next descent), the launches of bk_mcts_select_range,
+ * bk_leafnet_x3[_states] with the range's rows and bk_mcts_leaf_step_range. Range 0 runs on
+ * `stream`, the others on streams the bk_mcts owns, forked from `stream` and joined back to it
+ * with events before the call returns, so under stream capture the call becomes one graph with
+ * `groups` parallel branches. Trees are independent: the result is that of groups = 1, bitwise.
+ * ring = 1 adds scheduling edges between the branches (no data flows along them): a range's
+ * step of simulation s starts after the previous range's step of s, and range 0's step of s + 1
+ * after the last range's step of s, which keeps the ranges one step apart — while one range
+ * gathers policy rows the others are inside the net. ring = 2 adds only the edges of simulation 0
+ * (the ranges start one step apart and then run free); ring = 0 adds none.
+ * W [A][2NN], bias [A]: the policy Linear of bk_mcts_leaf_step (feat = net->pf, values =
+ * net->vout). obs: where the search writes the leaves' planes (net->obs, or NULL when the net
+ * reads states; net->status must then be leaf_status). n_sims = 0 creates the streams and
+ * launches nothing: call it once before a capture. After a failed launch the streams are still
+ * joined and the first error is returned. */
+int bk_mcts_sims_pipelined(bk_mcts* m, const bk_leafnet_args* net, int n_sims, int groups, int ring, const float* W,
+                           const float* bias, const void* roots, const int32_t* active, double cpuct,
+                           int32_t* leaf_status, float* obs, void* stream);
 
 #ifdef __cplusplus
 }
