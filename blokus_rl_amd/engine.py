@@ -90,6 +90,16 @@ _SIGS = {
     "bk_sparse_linear_dw": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "bk_ppo_gae": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, ctypes.c_float, ctypes.c_float, _vp, _vp, _vp]),
     "bk_filter_legal": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp]),
+    "bk_conv7_tile_boards": (_i, []),
+    "bk_conv7_weight_bytes": (_i, []),
+    "bk_conv7_pack": (_i, [_vp, _i, _vp, _vp, _vp]),
+    "bk_conv7": (_i, [_vp, _i, _vp, _vp, _vp, _vp, ctypes.c_float, _i, _vp, _vp]),
+    "bk_conv7_wgrad_workspace_floats": (_i, [_i]),
+    "bk_conv7_wgrad": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
+    "bk_conv7_first": (_i, [_vp, _i, _vp, _vp, _vp, ctypes.c_float, _i, _vp, _vp]),
+    "bk_conv7_first_wgrad": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
+    "bk_dropout_keep": (_i, [_vp, ctypes.c_int64, ctypes.c_float, _vp, _vp]),
+    "bk_conv7_act_grad": (_i, [_vp, _vp, ctypes.c_int64, ctypes.c_float, _vp, _vp]),
     "bk_bias_act": (_i, [_vp, ctypes.c_int64, _i, _vp, _vp, _i, _vp]),
     "bk_conv3x3_packed_floats": (_i, [_i]),
     "bk_conv3x3_form": (_i, [_i, _i]),

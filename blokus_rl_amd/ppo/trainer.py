@@ -13,6 +13,7 @@ Hyper-parameter names are PPOHparams' (hparams.py:97-185).
 from __future__ import annotations
 
 import ctypes
+import os
 import time
 from dataclasses import dataclass, field
 from pathlib import Path
@@ -160,13 +161,16 @@ class PPOTrainer:
     """PPOTrainer (trainer.py:20-400) with the device vector env instead of SyncVectorEnv."""
 
     def __init__(self, hparams: PPOHparams, device: str | torch.device | None = None, device_sampling: bool = True,
-                 channels_last: bool = False, phase_timers: bool = False):
+                 channels_last: bool = False, phase_timers: bool = False, device_convs: bool | None = None):
         """device_sampling: the rollout's draw in one kernel (bk_vec_policy) instead of torch's
         Categorical; channels_last: the cnn agent's convolutions in NHWC (off by default: measured
         round 6, MIOPEN_FIND_MODE=FAST, 8192 envs, 23.1 s per update against 2.0 s in NCHW — MIOpen
         then picks composable-kernel grouped convolutions instead of its NCHW implicit GEMMs;
         parameters and checkpoint keys are the same either way); phase_timers: synchronize and accumulate rollout / update seconds in
-        self.phase_s (benchmarking)."""
+        self.phase_s (benchmarking); device_convs: the cnn agent's ConvBlock on the device kernels
+        (ppo/device_conv.py: split-f16 MFMA convolutions with the Dropout and ReLU fused, NHWC
+        throughout) where the agent qualifies (7x7 boards, d_model 128; any other agent keeps
+        PyTorch's path); None reads BK_PPO_CONV from the environment (x3 = on), off by default."""
         self.hparams = hp = hparams
         self.device_sampling = device_sampling
         self.phase_timers = phase_timers
@@ -177,6 +181,12 @@ class PPOTrainer:
         self.agent = get_agent(hp.agent_type)(self.obs_shape, self.envs.single_action_space_n, hp).to(self.device)
         if channels_last and hp.agent_type == "cnn":
             self.agent = self.agent.to(memory_format=torch.channels_last)
+        if device_convs is None:
+            device_convs = os.environ.get("BK_PPO_CONV", "") == "x3"
+        self.device_convs = False
+        if device_convs and hp.agent_type == "cnn":
+            from .device_conv import is_prepared, prepare_agent
+            self.device_convs = is_prepared(prepare_agent(self.agent))
         self.optimizer = torch.optim.Adam(self.agent.parameters(), lr=hp.learning_rate, eps=hp.eps)
         self.memory = Memory(hp.num_steps, hp.num_envs, self.obs_shape, self.device)
         self.global_step = 0

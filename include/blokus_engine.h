@@ -387,6 +387,46 @@ int bk_ppo_gae(int T, int E, const float* rewards, const float* values, const fl
  * to 0 (illegal, or a legal logit of exactly 0, as in the reference) set to -1e9. x, out [E][A]. */
 int bk_filter_legal(const float* x, int E, int A, const uint64_t* mask, int mask_words, float* out, void* stream);
 
+/* ---------------------------------------------------------------- PPO cnn agent's ConvBlock
+ * ppo/agent.py:45-103 on 7x7 boards with d_model = 128 (ppoconv.hip): 1 -> 128 then 128 -> 128,
+ * 3x3, stride 1, padding 1, each followed by Dropout and ReLU. Activations are NHWC f32
+ * [B][7][7][128] (the dense buffer of a channels_last [B,128,7,7] tensor), 16-byte aligned.
+ *
+ * bk_conv7: the 128 -> 128 conv on split-f16 MFMA products (fp32-class accuracy, every board with
+ * its own power-of-two scale): y = conv(x) + bias, then, when keep != NULL, y *= keep bit *
+ * keep_scale, then, when relu != 0, y = max(y, 0). bias and keep may be NULL. keep: 4 x u32 per
+ * pixel, bit c of the 128 = channel c (bk_dropout_keep). wsplit (bk_conv7_weight_bytes() bytes)
+ * and inv [128] come from bk_conv7_pack (weight [128][128][3][3] f32, PyTorch's layout); the
+ * input gradient is the same call on dz with the weights packed with flip = 1
+ * (W[o][c][tap] = weight[c][o][8 - tap]). bk_conv7_tile_boards(): the boards that share one
+ * workgroup tile (a board's result never depends on its tile neighbours). */
+int bk_conv7_tile_boards(void);
+int bk_conv7_weight_bytes(void);
+int bk_conv7_pack(const float* w, int flip, void* wsplit, float* inv, void* stream);
+int bk_conv7(const float* x, int B, const void* wsplit, const float* inv, const float* bias, const uint32_t* keep,
+             float keep_scale, int relu, float* y, void* stream);
+/* The weight gradient dw[o][c][ky][kx] (PyTorch's layout, f32) = sum over b and pixels p of
+ * dz[b][p][o] * x[b][p + (ky - 1, kx - 1)][c] on split-f16 MFMA products; workspace:
+ * bk_conv7_wgrad_workspace_floats(B) floats (partial sums, added in a fixed order:
+ * deterministic). B = 0 gives zeros. */
+int bk_conv7_wgrad_workspace_floats(int B);
+int bk_conv7_wgrad(const float* x, const float* dz, int B, float* workspace, float* dw, void* stream);
+/* The first layer, 1 -> 128, in fp32 with a fixed summation order: x [B][49] f32, w [128][9]
+ * (weight [128][1][3][3]), y NHWC with bk_conv7's epilogue; its weight gradient dw [128][9] from x
+ * and dz [B][49][128] (workspace: bk_conv7_wgrad_workspace_floats(B) floats; deterministic). */
+int bk_conv7_first(const float* x, int B, const float* w, const float* bias, const uint32_t* keep, float keep_scale,
+                   int relu, float* y, void* stream);
+int bk_conv7_first_wgrad(const float* x, const float* dz, int B, float* workspace, float* dw, void* stream);
+/* Dropout keep bits for n_pixels pixels x 128 channels (4 x u32 per pixel, bit = kept), each kept
+ * with probability 1 - p: Philox-4x32-10 keyed by key[0] (its 32-bit halves), counter = (element
+ * index e lo, e hi, key[1] lo, key[1] hi) with e = (4 pixel + word) * 8 + j giving the random words of
+ * channels 32 word + 4 j .. + 3; kept when the word >= round(p 2^32). key: 2 x int64 on the
+ * device (no host synchronisation). p = 0 gives all ones. */
+int bk_dropout_keep(const int64_t* key, int64_t n_pixels, float p, uint32_t* keep, void* stream);
+/* The backward of the fused Dropout -> ReLU from the saved output: dz = gy * [y > 0] * keep_scale
+ * (y > 0 implies kept); n floats, a multiple of 4. */
+int bk_conv7_act_grad(const float* gy, const float* y, int64_t n, float keep_scale, float* dz, void* stream);
+
 /* ---------------------------------------------------------------- leaf-evaluator epilogue
  * The conv epilogues of the inference ResNet (models/blokus_nnet.py:135-151, BN folded):
  * in place on x[n] (NHWC, C channels innermost): x = act(x + bias[c] (+ residual)), act = ReLU
