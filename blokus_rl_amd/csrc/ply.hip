@@ -8,7 +8,9 @@
 //   (np.random.choice(len(pi), p=pi), trainer.py:125) by inverse CDF over the float32
 //   probabilities, and the per-ply record fields (int16 ids, float32 pi, mover, active flag).
 //   Random numbers: counter-based (splitmix64 of seed, ply, game, draw index), so a ply's draws do
-//   not depend on launch order; the law is pinned statistically
+//   not depend on launch order and a host restatement predicts every one of them: noise, float32
+//   pi and actions are compared draw for draw with oracle/ply_oracle.py (tests/test_ply_gpu.py,
+//   whose own law tests/test_ply_oracle.py pins), and statistically on whole games
 //   (tests/test_selfplay_gpu.py::test_play_ply_sampling_statistics). Gamma(alpha) by
 //   Marsaglia-Tsang (alpha = 1: an exact exponential draw), bounded retries.
 // * k_ply_finish — one workgroup for the batch: the games that ended this ply record z (the

@@ -160,3 +160,62 @@ def test_nan_priors_flag_an_error_instead_of_faulting(engines):
     torch.cuda.synchronize()
     with pytest.raises(EngineError):
         m.check()
+
+
+def test_root_policy_temperatures_and_cap_overflow():
+    """k_root beyond temperatures 0 and 1 (bit-exact above): after a short 7x7 search with
+    peaked priors, root_policy(T) for T in {0.5, 2} against NumPy float64 from root_stats' N —
+    N ** (1/T), a left-to-right sum, a quotient. N = 0 gives exactly 0, N = 1 bypasses pow; the
+    rest within 2^-50 relative (4 ulp: the device pow's ~1 ulp, the total, the quotient, one
+    spare). A call with cap below a root's K returns counts = -K and the full call's first cap
+    ids and pi values bitwise."""
+    from blokus_rl_amd.alphazero.batched_mcts import BatchedMCTS
+    from blokus_rl_amd.boards import random_boards
+    from blokus_rl_amd.engine import Engine
+
+    eng = Engine(7, 2, 5)
+    T = 8
+    m = BatchedMCTS(eng, T, node_cap=256, child_cap=T * 256 * 200)
+    roots = random_boards(eng, T, seed0=40, max_plies=4)
+    gen = torch.Generator(device=eng.device).manual_seed(1)
+    logits = torch.randn((T, eng.A), generator=gen, device=eng.device) * 3.0
+    vals = torch.zeros((T, eng.P), dtype=torch.float32, device=eng.device)
+    for _ in range(96):
+        m.select(roots, None, 1.0)
+        m.expand_backup(logits, vals, prior_mode=0)
+    m.check()
+    ids, n, _, _, counts = (x.cpu().numpy() for x in m.root_stats(roots))
+    assert (counts > 1).all()
+    seen = set()
+    worst = 0.0
+    for temp in (0.5, 2.0):
+        pid, pi, pc = (x.cpu().numpy() for x in m.root_policy(roots, None, temp))
+        assert (pc == counts).all()
+        for t in range(T):
+            K = int(counts[t])
+            nt = n[t, :K].astype(np.float64)
+            seen.update(np.minimum(n[t, :K], 2).tolist())
+            terms = nt ** (1.0 / temp)
+            total = 0.0
+            for v in terms:
+                total += float(v)
+            ref = terms / total
+            got = pi[t, :K]
+            assert (pid[t, :K] == ids[t, :K]).all() and not pi[t, K:].any()
+            assert (got[nt == 0] == 0).all()
+            rel = np.abs(got[nt > 0] / ref[nt > 0] - 1.0)
+            worst = max(worst, float(rel.max()))
+            assert abs(got.sum() - 1.0) < 1e-12
+    print(f"k_root: largest relative distance to float64 NumPy {worst:.3e} = {worst / 2.0 ** -52:.2f} ulp "
+          f"(bar {2.0 ** -50:.3e})")
+    assert seen == {0, 1, 2}, seen  # unvisited children, single visits and the pow branch all occur
+    assert worst <= 2.0 ** -50
+    for temp in (2.0, 1.0, 0.0):
+        fid, fpi, _ = (x.cpu().numpy() for x in m.root_policy(roots, None, temp))
+        for t in (0, T - 1):
+            K = int(counts[t])
+            cap = K // 2
+            cid, cpi, cc = (x.cpu().numpy() for x in m.root_policy(roots, None, temp, cap=cap))
+            assert cc[t] == -K
+            assert (cc == np.where(counts <= cap, counts, -counts)).all()
+            assert cid[t].tobytes() == fid[t, :cap].tobytes() and cpi[t].tobytes() == fpi[t, :cap].tobytes()
