@@ -50,7 +50,7 @@ class LeafEvaluator:
     v [G, P] f32). DumbNet needs no forward: a constant uniform log-prior and zero values."""
 
     def __init__(self, model: torch.nn.Module | None, eng: Engine, G: int, dtype: torch.dtype = torch.float32,
-                 use_graph: bool = True, sparse_policy: bool = True):
+                 use_graph: bool = True, sparse_policy: bool = True, x3_boards: str | None = None):
         self.model = model
         self.eng = eng
         self.G = G
@@ -69,7 +69,8 @@ class LeafEvaluator:
         # raw policy logits are enough: k_expand_backup takes the softmax over the legal ids; with
         # the HIP ResNet, even the policy Linear is left to the search (bk_mcts_leaf_logits computes
         # only the leaf's legal ids' logits), so the net returns (policy features, v)
-        self.model = inference_model(model, normalize=False, dtype=dtype, features=sparse_policy).to(
+        self.model = inference_model(model, normalize=False, dtype=dtype, features=sparse_policy,
+                                     x3_boards=x3_boards).to(
             memory_format=torch.channels_last)
         self.sparse = isinstance(self.model, LeafResNet) and self.model.native and sparse_policy
         if isinstance(self.model, LeafResNet) and not self.sparse:
@@ -160,7 +161,7 @@ class SelfPlay:
                  cap: int = 2048, seed: int = 0, nn_dtype: torch.dtype = torch.float32, use_graph: bool = True,
                  continuous: bool = False, sim_graph_sims: int | None = None, record_plies: int | None = None,
                  leaf_input: str | None = None, sim_groups: int | None = None, sim_ring: int | bool | None = None,
-                 sim_groups_min_games: int = 64):
+                 sim_groups_min_games: int = 64, x3_boards: str | None = None):
         self.eng = eng
         self.G = games
         self.num_sims = num_sims
@@ -181,7 +182,9 @@ class SelfPlay:
         if node_cap is None:
             node_cap = self.node_cap_for(eng, num_sims)
         self.mcts = BatchedMCTS(eng, games, node_cap=node_cap, child_cap=child_cap)
-        self.evaluator = LeafEvaluator(model, eng, games, nn_dtype, use_graph)
+        # x3_boards / BK_X3_BOARDS "all": the one-launch split-f16 leaf net (and with it leaf_input
+        # "states" and the pipelined groups) also for 2- and 3-player nets and 7x7 boards
+        self.evaluator = LeafEvaluator(model, eng, games, nn_dtype, use_graph, x3_boards=x3_boards)
         self._use_graph = use_graph
         # what the leaf net reads: "planes" (the f32 observation the search writes per leaf) or
         # "states" (the search's packed leaf states and status: no observation is written inside the

@@ -325,6 +325,41 @@ def pack_x3(w: torch.Tensor, b: torch.Tensor | None = None) -> tuple[torch.Tenso
     return packed.view(torch.uint8).view(-1).to(w.device), inv.to(w.device).contiguous(), bound.to(w.device)
 
 
+def pack_x3_stem(w: torch.Tensor, b: torch.Tensor | None = None) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """pack_x3 of a stem with fewer than 8 input planes ([64, 2P, 3, 3], P < 4): the input channels
+    zero-padded to 8, which is exact (the padded products are +-0) and leaves the row maxima, and
+    so the scales and the bound, those of the unpadded weights. bk_leafnet_x3_np's wstem."""
+    cin = w.shape[1]
+    assert w.shape[0] == 64 and w.shape[2:] == (3, 3) and 0 < cin <= 8
+    if cin < 8:
+        w = torch.cat([w.detach(), w.detach().new_zeros(64, 8 - cin, 3, 3)], dim=1)
+    return pack_x3(w, b)
+
+
+def x3_boards_mode(arg: str | None = None) -> str:
+    """Which board shapes take the one-launch split-f16 leaf net: "classic" (default) = 8 planes
+    (4 players) on 14x14 / 20x20, bk_leafnet_x3 only; "all" = also 2 and 3 players and 7x7
+    (bk_leafnet_x3_np). arg, else BK_X3_BOARDS."""
+    import os
+
+    m = arg if arg is not None else os.environ.get("BK_X3_BOARDS", "classic")
+    if m not in ("classic", "all"):
+        raise ValueError(f"x3_boards / BK_X3_BOARDS must be classic or all, got {m!r}")
+    return m
+
+
+def x3_pack() -> int:
+    """bk_leafnet_x3_np's boards_per_wg: 0 (default) = chosen from the batch size, 1 = one board
+    per workgroup, 4 = four (7x7 only); BK_X3_PACK, for tests and A/B runs. The outputs do not
+    depend on it (bitwise)."""
+    import os
+
+    k = int(os.environ.get("BK_X3_PACK", "0"))
+    if k not in (0, 1, 4):
+        raise ValueError(f"BK_X3_PACK must be 0, 1 or 4, got {k}")
+    return k
+
+
 def pack_w3(w: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
     """[64, 64, 3, 3] tower conv weights -> bk_leafnet_w3's operands: the Winograd F(2x2,3x3)
     transform U = G w G^T (fp64), each output channel's row scaled by 2^e_o so that its largest
@@ -362,12 +397,14 @@ def net_math() -> str:
 
 def leafnet_x3(obs: torch.Tensor, model: "LeafResNet", want_out: bool = False):
     """bk_leafnet_x3: the planar observation [B, 8, N, N] -> (policy features [B, 2*N*N], values
-    [B, P][, tower output [B, 64, N, N] channels_last]) in one launch."""
+    [B, P][, tower output [B, 64, N, N] channels_last]) in one launch. A model whose x3 entry for
+    N is "np" (LeafResNet.x3_entry: x3_boards "all") takes [B, 2P, N, N] through bk_leafnet_x3_np."""
     from .engine import _check, _ptr, _stream, load_library
 
     B, cin, N, _ = obs.shape
-    assert cin == 8 and obs.dtype == torch.float32 and obs.is_contiguous()
     f = model.f
+    np_entry = model.x3_entry(N) == "np"
+    assert cin == (f.stem.in_channels if np_entry else 8) and obs.dtype == torch.float32 and obs.is_contiguous()
     lib = load_library()
     nl = 2 * len(f.blocks)
     assert model.x3_wtower.numel() == nl * lib.bk_leafnet_x3_weight_bytes(64)
@@ -378,11 +415,18 @@ def leafnet_x3(obs: torch.Tensor, model: "LeafResNet", want_out: bool = False):
     out = torch.empty((B, 64, N, N), dtype=torch.float32, device=obs.device,
                       memory_format=torch.channels_last) if want_out else None
     h = model.x3_heads
+    optr = None if out is None else ctypes.c_void_p(out.data_ptr())
+    if np_entry:
+        _check(lib.bk_leafnet_x3_np(
+            ctypes.c_void_p(obs.data_ptr()), B, N, cin, _ptr(model.x3_wstem), _ptr(model.x3_sstem), _ptr(h[0]), nl,
+            _ptr(model.x3_wtower), _ptr(model.x3_stower), _ptr(model.b_tower), _ptr(model.x3_bounds),
+            *[_ptr(t) for t in h[1:]], P, _ptr(pf), _ptr(v), optr, x3_pack(), _stream(obs.device)))
+        return (pf, v, out) if want_out else (pf, v)
     _check(lib.bk_leafnet_x3(
         ctypes.c_void_p(obs.data_ptr()), B, N, cin, _ptr(model.x3_wstem), _ptr(model.x3_sstem), _ptr(h[0]), nl,
         _ptr(model.x3_wtower), _ptr(model.x3_stower), _ptr(model.b_tower), _ptr(model.x3_bounds),
         *[_ptr(t) for t in h[1:]], P, _ptr(pf),
-        _ptr(v), None if out is None else ctypes.c_void_p(out.data_ptr()), _stream(obs.device)))
+        _ptr(v), optr, _stream(obs.device)))
     return (pf, v, out) if want_out else (pf, v)
 
 
@@ -416,11 +460,17 @@ def leafnet_x3_states(states, status: torch.Tensor | None, model: "LeafResNet", 
     out = torch.empty((B, 64, N, N), dtype=torch.float32, device=dev,
                       memory_format=torch.channels_last) if want_out else None
     h = model.x3_heads
+    optr = None if out is None else ctypes.c_void_p(out.data_ptr())
+    if model.x3_entry(N) == "np":
+        _check(lib.bk_leafnet_x3_np_states(
+            sptr, _ptr(status), B, N, f.stem.in_channels // 2, _ptr(model.x3_wstem), _ptr(model.x3_sstem),
+            _ptr(h[0]), nl, _ptr(model.x3_wtower), _ptr(model.x3_stower), _ptr(model.b_tower),
+            _ptr(model.x3_bounds), *[_ptr(t) for t in h[1:]], _ptr(pf), _ptr(v), optr, x3_pack(), _stream(dev)))
+        return (pf, v, out) if want_out else (pf, v)
     _check(lib.bk_leafnet_x3_states(
         sptr, _ptr(status), B, N, f.stem.in_channels // 2, _ptr(model.x3_wstem), _ptr(model.x3_sstem), _ptr(h[0]), nl,
         _ptr(model.x3_wtower), _ptr(model.x3_stower), _ptr(model.b_tower), _ptr(model.x3_bounds),
-        *[_ptr(t) for t in h[1:]], _ptr(pf), _ptr(v),
-        None if out is None else ctypes.c_void_p(out.data_ptr()), _stream(dev)))
+        *[_ptr(t) for t in h[1:]], _ptr(pf), _ptr(v), optr, _stream(dev)))
     return (pf, v, out) if want_out else (pf, v)
 
 
@@ -436,7 +486,8 @@ def leafnet_x3_args(model: "LeafResNet", pf: torch.Tensor, v: torch.Tensor, obs:
     f = model.f
     lib = load_library()
     N, P, nl = model.board_size, f.value_fc2.out_features, 2 * len(f.blocks)
-    assert model.x3 and f.stem.in_channels == 2 * P and lib.bk_leafnet_x3_supported(N)
+    entry = model.x3_entry(N)
+    assert model.x3 and f.stem.in_channels == 2 * P and entry is not None
     assert model.x3_wtower.numel() == nl * lib.bk_leafnet_x3_weight_bytes(64)
     assert model.x3_wstem.numel() == lib.bk_leafnet_x3_weight_bytes(8)
     B = pf.shape[0]
@@ -452,6 +503,7 @@ def leafnet_x3_args(model: "LeafResNet", pf: torch.Tensor, v: torch.Tensor, obs:
         a.states = states.data_ptr() if isinstance(states, torch.Tensor) else int(states)
         a.status = status.data_ptr()
     a.N, a.P, a.nlayers = N, P, nl
+    a.np = x3_pack() + 1 if entry == "np" else 0  # bk_leafnet_x3_np[_states] with boards_per_wg = np - 1
     h = model.x3_heads
     tensors = {"wstem": model.x3_wstem, "sstem": model.x3_sstem, "bstem": h[0], "wtower": model.x3_wtower,
                "stower": model.x3_stower, "btower": model.b_tower, "bounds": model.x3_bounds, "pf": pf, "vout": v}
@@ -617,8 +669,11 @@ class LeafResNet(nn.Module):
     comes back as raw logits (the leaf batch's consumer, k_expand_backup, takes a softmax over the
     legal ids, which a per-row shift does not change), skipping the full-row log-softmax."""
 
-    def __init__(self, net: ResNet, normalize: bool = True, features: bool = False):
+    def __init__(self, net: ResNet, normalize: bool = True, features: bool = False, x3_boards: str | None = None):
         super().__init__()
+        # "all": the one-launch split-f16 net also for 2- and 3-player stems and 7x7 boards
+        # (bk_leafnet_x3_np); "classic" (default): exactly the 8-plane 14x14 / 20x20 form
+        self.x3_boards = x3_boards_mode(x3_boards)
         self.f = FusedResNet(net).eval()
         self.normalize = normalize
         self.features = features  # return (policy features [B, 2*N*N], v): the search applies policy_out
@@ -636,9 +691,9 @@ class LeafResNet(nn.Module):
                 convs = [c for blk in f.blocks for c in blk]
                 self.register_buffer("u_tower", pack_tower([c.weight.detach() for c in convs]))
                 self.register_buffer("b_tower", torch.cat([c.bias.detach().float() for c in convs]).contiguous())
-            self.x3 = f.stem.in_channels == 8 and len(f.blocks) > 0
+            self.x3 = (f.stem.in_channels == 8 or self.x3_boards == "all") and len(f.blocks) > 0
             if self.x3:  # bk_leafnet_x3's operands: split f16 weights + inverse scales
-                ws, ss, bs = pack_x3(f.stem.weight, f.stem.bias)
+                ws, ss, bs = pack_x3_stem(f.stem.weight, f.stem.bias)
                 self.register_buffer("x3_wstem", ws)
                 self.register_buffer("x3_sstem", ss)
                 packs = [pack_x3(c.weight, c.bias) for c in convs]
@@ -670,11 +725,24 @@ class LeafResNet(nn.Module):
 
         return math.isqrt(self.f.value_fc1.in_features)
 
-    def takes_states(self) -> bool:
-        """Whether forward_states runs bk_leafnet_x3_states (else it observes and calls forward)."""
+    def x3_entry(self, N: int) -> str | None:
+        """The one-launch split-f16 kernel of an N x N board for this net: "classic"
+        (bk_leafnet_x3[_states]: 8 planes on 14x14 / 20x20), "np" (bk_leafnet_x3_np[_states], with
+        x3_boards "all": the shapes the classic entries refuse) or None (the f32 kernels)."""
         from .engine import load_library
 
-        return bool(self.x3 and net_math() == "x3" and load_library().bk_leafnet_x3_supported(self.board_size))
+        if not self.x3:
+            return None
+        lib, cin = load_library(), self.f.stem.in_channels
+        if cin == 8 and lib.bk_leafnet_x3_supported(N):
+            return "classic"
+        if self.x3_boards == "all" and cin % 2 == 0 and lib.bk_leafnet_x3_np_supported(N, cin // 2):
+            return "np"
+        return None
+
+    def takes_states(self) -> bool:
+        """Whether forward_states runs bk_leafnet_x3_states (else it observes and calls forward)."""
+        return bool(self.x3 and net_math() == "x3" and self.x3_entry(self.board_size) is not None)
 
     @torch.no_grad()
     def forward_states(self, states: torch.Tensor, status: torch.Tensor | None = None):
@@ -703,14 +771,14 @@ class LeafResNet(nn.Module):
             from .engine import load_library
 
             math = net_math() if self.x3 else "f32"
-            if math == "w3" and load_library().bk_leafnet_w3_supported(x.shape[2]):
+            if math == "w3" and f.stem.in_channels == 8 and load_library().bk_leafnet_w3_supported(x.shape[2]):
                 # the tower as Winograd convolutions on split-f16 MFMA products (bk_leafnet_w3)
                 pf, v = leafnet_w3(x.float().contiguous(), self)
                 if self.features:
                     return pf, v
                 logits = f.policy_out(pf)
                 return (F.log_softmax(logits, dim=1) if self.normalize else logits), v
-            if math in ("x3", "w3") and load_library().bk_leafnet_x3_supported(x.shape[2]):
+            if math in ("x3", "w3") and self.x3_entry(x.shape[2]) is not None:
                 # the whole net in one launch on split-f16 MFMA products (bk_leafnet_x3)
                 pf, v = leafnet_x3(x.float().contiguous(), self)
                 if self.features:
@@ -762,13 +830,13 @@ class LeafResNet(nn.Module):
 
 
 def inference_model(model: nn.Module, normalize: bool = True, dtype: torch.dtype = torch.float32,
-                    features: bool = False) -> nn.Module:
+                    features: bool = False, x3_boards: str | None = None) -> nn.Module:
     """The leaf evaluator's form of a net: ResNet -> LeafResNet (fp32 HIP kernels) on a HIP
     device, FusedResNet for reduced-precision autocast runs or off the device; eval() otherwise.
     normalize=False lets LeafResNet return raw policy logits (see LeafResNet)."""
     if isinstance(model, ResNet):
         dev = next(model.parameters()).device
         if dev.type == "cuda" and dtype == torch.float32:
-            return LeafResNet(model, normalize=normalize, features=features).eval()
+            return LeafResNet(model, normalize=normalize, features=features, x3_boards=x3_boards).eval()
         return FusedResNet(model).eval()
     return model.eval()

@@ -512,6 +512,27 @@ int bk_leafnet_x3_states(const void* states, const int32_t* status, int B, int N
                          const float* bp, const float* wv, const float* bv, const float* w1t, const float* b1,
                          const float* w2, const float* b2, float* pf, float* vout, float* out, void* stream);
 
+/* bk_leafnet_x3 / bk_leafnet_x3_states for the other board shapes (leafnet_np.hip): N = 7, 14 or
+ * 20 with P = 2, 3 or 4 players (bk_leafnet_x3_np_supported). obs is [B][2P][N][N] (cin = 2P);
+ * wstem is still the 8-channel stem pack, the stem's input channels zero-padded from 2P to 8
+ * (nets.py pack_x3_stem); every other operand as bk_leafnet_x3[_states]. boards_per_wg: 1 = one
+ * board per workgroup, 4 = four boards per workgroup (N = 7 only: four 7x7 boards share one
+ * activation grid, so each weight fragment read from L2 feeds four boards), 0 = chosen from B.
+ * A board's pf, vout and out rows are a function of that board alone: bitwise equal for either
+ * boards_per_wg, any B and any neighbours. Rows past B are never written. */
+int bk_leafnet_x3_np_supported(int N, int P);
+int bk_leafnet_x3_np(const float* obs, int B, int N, int cin, const void* wstem, const float* sstem,
+                     const float* bstem, int nlayers, const void* wtower, const float* stower, const float* btower,
+                     const float* bounds, const float* wp, const float* bp, const float* wv, const float* bv,
+                     const float* w1t, const float* b1, const float* w2, const float* b2, int P, float* pf,
+                     float* vout, float* out, int boards_per_wg, void* stream);
+int bk_leafnet_x3_np_states(const void* states, const int32_t* status, int B, int N, int P, const void* wstem,
+                            const float* sstem, const float* bstem, int nlayers, const void* wtower,
+                            const float* stower, const float* btower, const float* bounds, const float* wp,
+                            const float* bp, const float* wv, const float* bv, const float* w1t, const float* b1,
+                            const float* w2, const float* b2, float* pf, float* vout, float* out, int boards_per_wg,
+                            void* stream);
+
 /* The same network and outputs as bk_leafnet_x3 with the residual tower as Winograd F(2x2,3x3)
  * convolutions on the same split-f16 products (leafnet_w3.hip: 16 products per 2x2 output tile
  * instead of 36). utower: nlayers x bk_leafnet_w3_weight_bytes() bytes of split U = G g G^T per
@@ -553,6 +574,7 @@ typedef struct bk_leafnet_args {
   const float* b2;
   float* pf;
   float* vout;
+  int np; /* 0: bk_leafnet_x3[_states]; boards_per_wg + 1 (1, 2 or 5): bk_leafnet_x3_np[_states] */
 } bk_leafnet_args;
 
 /* n_sims simulations of every tree, the trees split into `groups` (1, 2 or 4) contiguous ranges
