@@ -16,9 +16,21 @@ the tree of the player to move is active in each game. The G leaves of a simulat
 gathered into one [G, 2P, N, N] batch; each distinct net evaluates it once (the arena compare
 has two: the new net and the previous one) and rows are picked per game by the seat's net.
 DumbNet seats (the "uninformed MCTS" player) get the uniform log-prior and zero values.
+
+path="graph" (or BK_ARENA=graph; default "eager", the loop above): a ply's simulations are one
+captured, linear graph of select_rows + max_sims x {leafnet_x3_rows, leaf_step_rows}
+(bk_arena_sims): one workgroup per game finds its tree, its net and its budget in three device
+tables, so an N-net match evaluates one net per leaf, with the sparse policy head, and the ply's
+tail is arena_move, next_state, game_ended and arena_finish with no host sync (the host reads the
+count of running games every 8 plies). Net seats need the packed-state split-f16 leaf net
+(LeafResNet.takes_states) and nets of one shape; otherwise the arena plays the eager path and
+says why in path_reason. The sparse head's logits differ from the dense head's in the last bits,
+so games with net seats may diverge between the two paths (both fp32-class); uninformed seats
+are exact.
 """
 from __future__ import annotations
 
+import os
 from itertools import permutations
 
 import numpy as np
@@ -46,9 +58,27 @@ def seat_of(player) -> ArenaSeat:
     return ArenaSeat(model, player.simulations)
 
 
+def arena_finish_np(to_move, ended, scores, status, orders, seat_net, seat_sims, over, final, illegal=0):
+    """bk_arena_finish restated in NumPy (the tests' oracle): from the next states' to_move [R],
+    game_ended's ended [R] / scores [R, P], next_state's status [R], and the running over [R] /
+    final [R, P] / illegal -> (tree_of_row, net_of_row, sims_of_row, over, final, illegal, running)."""
+    to_move, ended, status = np.asarray(to_move), np.asarray(ended) != 0, np.asarray(status)
+    orders, over = np.asarray(orders), np.asarray(over) != 0
+    R, P = orders.shape
+    illegal = int(bool(illegal) or bool(((status != 0) & ~over).any()))
+    final = np.where((ended & ~over)[:, None], np.asarray(scores, dtype=np.float64), np.asarray(final, dtype=np.float64))
+    over = over | ended
+    player = orders[np.arange(R), to_move]
+    tree = np.where(over, -1, np.arange(R) * P + player).astype(np.int32)
+    net = np.asarray(seat_net)[player].astype(np.int32)
+    sims = np.asarray(seat_sims)[player].astype(np.int32)
+    return tree, net, sims, over.astype(np.uint8), final, illegal, int((~over).sum())
+
+
 class BatchedArena:
     def __init__(self, eng: Engine, seats: list, cpuct: float = 1.0, node_cap: int | None = None,
-                 child_cap_per_tree: int | None = None, nn_dtype: torch.dtype = torch.float32):
+                 child_cap_per_tree: int | None = None, nn_dtype: torch.dtype = torch.float32,
+                 path: str | None = None, record_actions: bool = False, x3_boards: str | None = None):
         self.eng = eng
         self.seats = [s if isinstance(s, ArenaSeat) else seat_of(s) for s in seats]
         if len(self.seats) != eng.P:
@@ -61,6 +91,15 @@ class BatchedArena:
         self.node_cap = node_cap
         self.child_cap_per_tree = child_cap_per_tree or node_cap * (256 if eng.N >= 14 else 64)
         self.nn_dtype = nn_dtype
+        self.path = path if path is not None else os.environ.get("BK_ARENA", "eager")
+        if self.path not in ("eager", "graph"):
+            raise ValueError(f"path / BK_ARENA must be eager or graph, got {self.path!r}")
+        self.path_reason = ""       # why a requested graph path fell back to eager ("" = it did not)
+        self.path_used = None       # the path the last play() took
+        self.record_actions = record_actions
+        self.last_actions = None    # record_actions (graph path): [plies, G] int32, -1 = no move
+        self.counters = None        # graph path: the search's counters after the last play()
+        self.x3_boards = x3_boards  # the leaf net's board coverage (None: each model's own / BK_X3_BOARDS)
         # distinct nets (by identity) -> evaluator index; seat -> net index
         self._models: list = []
         self.seat_net = []
@@ -78,6 +117,12 @@ class BatchedArena:
 
     def play(self, games_num: int, permute: bool = False, max_plies: int = 10_000):
         """-> (scores float64[P] accumulated per player, per-game score rows [G][P], final states)."""
+        self.path_used = "eager"
+        if self.path == "graph":
+            evals = self._graph_evaluators()
+            if evals is not None:
+                self.path_used = "graph"
+                return self._play_graph(games_num, permute, max_plies, evals)
         eng, P, G = self.eng, self.eng.P, games_num
         dev = eng.device
         matches = list(permutations(range(P))) if permute else [tuple(range(P))]
@@ -144,18 +189,118 @@ class BatchedArena:
             if bool(over.all()):
                 break
         mcts.check()
+        return self._totals(final, orders, states)
+
+    def _totals(self, final, orders, states):
+        P = self.eng.P
         per_game = final.cpu().numpy()
         ords = orders.cpu().numpy()
         total = np.zeros(P)
-        for g in range(G):
+        for g in range(per_game.shape[0]):
             total[list(ords[g])] += per_game[g]
         return total, per_game, states
 
+    # ------------------------------------------------------------------ path="graph"
+    def _graph_evaluators(self):
+        """One sparse LeafEvaluator per distinct net seat, or None (and path_reason) when the graph
+        path cannot take these seats."""
+        from ..engine import ARENA_MAX_NETS
+
+        self.path_reason = ""
+        models = [m for m in self._models if m is not None]
+        if len(models) > ARENA_MAX_NETS:
+            self.path_reason = f"{len(models)} distinct nets, the net table holds {ARENA_MAX_NETS}"
+            return None
+        evals = []
+        for m in models:
+            ev = LeafEvaluator(m, self.eng, 1, self.nn_dtype, use_graph=False, sparse_policy=True,
+                               x3_boards=self.x3_boards if self.x3_boards is not None else getattr(m, "x3_boards", None))
+            if not ev.takes_states:
+                self.path_reason = (f"{type(m).__name__} seat: no packed-state split-f16 leaf net for it "
+                                    f"({self.eng.N}x{self.eng.N}, {self.eng.P} players, x3_boards / BK_NET_MATH)")
+                return None
+            evals.append(ev)
+        if evals:
+            from ..nets import leafnet_x3_table
+            try:  # the shapes only; the real table is built on the match's buffers
+                dev = self.eng.device
+                F = 2 * self.eng.N * self.eng.N
+                leafnet_x3_table([ev.model for ev in evals], torch.empty((1, F), device=dev),
+                                 torch.empty((1, self.eng.P), device=dev), torch.empty((1, 384), dtype=torch.uint8, device=dev),
+                                 torch.zeros(1, dtype=torch.int32, device=dev))
+            except (ValueError, AssertionError) as e:
+                self.path_reason = f"the nets do not fit one table: {e}"
+                return None
+        return evals
+
+    def _play_graph(self, games_num: int, permute: bool, max_plies: int, evals: list):
+        from ..engine import arena_heads, arena_rows
+        from ..nets import leafnet_x3_table
+
+        eng, P, G = self.eng, self.eng.P, games_num
+        dev = eng.device
+        i32 = dict(dtype=torch.int32, device=dev)
+        matches = list(permutations(range(P))) if permute else [tuple(range(P))]
+        orders = torch.tensor([matches[i % len(matches)] for i in range(G)], **i32)  # [G,P]
+        T = G * P
+        mcts = BatchedMCTS(eng, T, node_cap=self.node_cap, child_cap=T * self.child_cap_per_tree)
+        # seat -> index into the table of net seats, -1 = uninformed
+        informed = [i for i, m in enumerate(self._models) if m is not None]
+        seat_net = torch.tensor([informed.index(n) if n in informed else -1 for n in self.seat_net], **i32)
+        seat_sims = torch.tensor([s.simulations for s in self.seats], **i32)
+        max_sims = max(s.simulations for s in self.seats)
+        pf = torch.zeros((T, 2 * eng.N * eng.N), dtype=torch.float32, device=dev)
+        vout = torch.zeros((T, P), dtype=torch.float32, device=dev)
+        table = leafnet_x3_table([ev.model for ev in evals], pf, vout, mcts.leaf_states_ptr, mcts.status) if evals else None
+        heads = arena_heads([(ev.policy_w, ev.policy_b) for ev in evals])
+        roots = eng.init_states(G)
+        nxt = eng.empty_states(G)
+        tabs = [torch.full((G,), -1, **i32) for _ in range(3)]
+        rows = arena_rows(*tabs, T)
+        over = torch.zeros(G, dtype=torch.uint8, device=dev)
+        final = torch.zeros((G, P), dtype=torch.float64, device=dev)
+        ended = torch.zeros(G, **i32)
+        scores = torch.zeros((G, P), dtype=torch.float64, device=dev)
+        status = torch.zeros(G, **i32)
+        nplayer = torch.zeros(G, **i32)
+        action = torch.full((G,), -1, **i32)
+        illegal = torch.zeros(1, **i32)
+        running = torch.zeros(1, **i32)
+        # every row is dead here: one uncaptured pass that launches everything and touches nothing
+        mcts.arena_sims(table, rows, max_sims, heads, pf, vout, roots, self.cpuct)
+        torch.cuda.synchronize(dev)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            mcts.arena_sims(table, rows, max_sims, heads, pf, vout, roots, self.cpuct)
+        # the first ply's tables from the initial states (nothing ended, nothing illegal)
+        eng.arena_finish(roots, ended, scores, status, orders, seat_net, seat_sims, *tabs, over, final, illegal, running)
+        acts = [] if self.record_actions else None
+        for ply in range(max_plies):
+            graph.replay()
+            mcts.arena_move(rows, roots, action)
+            if acts is not None:
+                acts.append(action.clone())
+            eng.next_state_into(roots, action, nxt, nplayer, status)
+            eng.game_ended_into(nxt, ended, scores)
+            eng.arena_finish(nxt, ended, scores, status, orders, seat_net, seat_sims, *tabs, over, final, illegal,
+                             running)
+            roots.copy_(nxt)
+            if ply % 8 == 7 and int(running.item()) == 0:
+                break
+        if acts is not None:
+            a = torch.stack(acts).cpu().numpy() if acts else np.zeros((0, G), dtype=np.int32)
+            live = (a >= 0).any(axis=1)
+            self.last_actions = a[: int(np.nonzero(live)[0].max()) + 1] if live.any() else a[:0]
+        if int(illegal.item()):
+            raise RuntimeError("arena: an MCTS move was illegal")
+        self.counters = mcts.check()
+        return self._totals(final, orders.long(), roots)
+
 
 def play_match_batched(game, players: list, games_num: int, permute: bool = False, cpuct: float = 1.0,
-                       node_cap: int | None = None):
+                       node_cap: int | None = None, path: str | None = None):
     """play_match(game, players, games_num, permute) (arena.py:10-32) for MCTSPlayer seats,
     batched: -> (scores, items) with items[i] = {"scores": game i's one-hot, "frames": []}."""
-    arena = BatchedArena(game.engine, players, cpuct=cpuct, node_cap=node_cap)
+    arena = BatchedArena(game.engine, players, cpuct=cpuct, node_cap=node_cap, path=path)
     scores, per_game, _ = arena.play(games_num, permute)
     return scores, [{"scores": per_game[i], "frames": []} for i in range(games_num)]

@@ -143,6 +143,48 @@ class BatchedMCTS:
                                                _ptr(weight), _ptr(bias), _ptr(roots), _ptr(active), float(cpuct),
                                                _ptr(self.status), _ptr(obs), self._s()))
 
+    # ---- the arena's rows entries: one workgroup per game, tree / net / budget from device tables
+    # (engine.arena_rows); roots is [R, 384], indexed by row
+    def select_rows(self, rows, roots: torch.Tensor, cpuct: float = 1.0):
+        """The descent of simulation 0 for every live row (bk_mcts_select_rows): leaf states and
+        status only, no observation planes, no mask copy."""
+        assert roots.shape[0] == rows.R
+        _check(self.lib.bk_mcts_select_rows(self.h, ctypes.byref(rows), _ptr(roots), float(cpuct), _ptr(self.status),
+                                            self._s()))
+        return self.status
+
+    def leaf_step_rows(self, rows, sim: int, feat: torch.Tensor, heads, values: torch.Tensor,
+                       roots: torch.Tensor | None = None, cpuct: float = 1.0):
+        """leaf_step() for every row live at `sim` with the policy head of the row's net
+        (engine.arena_heads; net -1: zero logits and values); with roots, also the next descent of
+        the rows whose budget is not exhausted (bk_mcts_leaf_step_rows). feat [T, F], values [T, P]."""
+        assert feat.dtype == torch.float32 and feat.shape[0] == self.T and feat.stride(1) == 1
+        assert values.dtype == torch.float32 and values.shape == (self.T, self.eng.P)
+        sel = roots is not None
+        _check(self.lib.bk_mcts_leaf_step_rows(self.h, ctypes.byref(rows), int(sim), ctypes.c_void_p(feat.data_ptr()),
+                                               feat.stride(0), feat.shape[1], ctypes.byref(heads), _ptr(values),
+                                               int(sel), _ptr(roots), float(cpuct),
+                                               _ptr(self.status) if sel else None, self._s()))
+
+    def arena_move(self, rows, roots: torch.Tensor, action: torch.Tensor | None = None) -> torch.Tensor:
+        """The T = 0 move of every live row straight from its tree (bk_arena_move): the id of the
+        first child with maximal N, -1 for a dead row or a root without children."""
+        if action is None:
+            action = torch.empty(rows.R, dtype=torch.int32, device=self.eng.device)
+        assert action.dtype == torch.int32 and action.shape == (rows.R,) and roots.shape[0] == rows.R
+        _check(self.lib.bk_arena_move(self.h, ctypes.byref(rows), _ptr(roots), _ptr(action), self._s()))
+        return action
+
+    def arena_sims(self, net_table, rows, max_sims: int, heads, pf: torch.Tensor, vout: torch.Tensor,
+                   roots: torch.Tensor, cpuct: float = 1.0):
+        """A whole ply's search on the current stream, no forked branches (bk_arena_sims): select_rows,
+        then max_sims x {leafnet_x3_rows, leaf_step_rows}. net_table: nets.leafnet_x3_table (or None:
+        uninformed seats only); pf [T, F] / vout [T, P] are the nets' outputs."""
+        n = 0 if net_table is None else len(net_table)
+        assert pf.shape == (self.T, 2 * self.eng.N * self.eng.N) and vout.shape == (self.T, self.eng.P)
+        _check(self.lib.bk_arena_sims(self.h, net_table, n, ctypes.byref(rows), int(max_sims), ctypes.byref(heads),
+                                      _ptr(pf), _ptr(vout), _ptr(roots), float(cpuct), _ptr(self.status), self._s()))
+
     @property
     def leaf_states_ptr(self) -> int:
         """Device address of the search's own [T, 384] leaf-state buffer (bk_mcts_leaf_states): the

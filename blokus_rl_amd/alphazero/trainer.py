@@ -111,13 +111,13 @@ class AlphaZeroTrainer:
         expected = 1 / (1 + 10 ** ((opponent_elo - agent_elo) / 400))
         return agent_elo + self.hparams.elo_convert_rate * (1 - expected) * agent_score
 
-    def arena_compare(self, opponent_model=None, games: int | None = None):
+    def arena_compare(self, opponent_model=None, games: int | None = None, path: str | None = None):
         """_arena_compare (trainer.py:222-271): the agent's net against P-1 seats of the
         previous net (DumbNet/None = the uninformed MCTS opponent), batched, T=0 moves."""
         P = self.game.number_of_players
         sims = self.hparams.num_mcts_sims
         seats = [ArenaSeat(self.nnet.model.eval(), sims)] + [ArenaSeat(opponent_model, sims) for _ in range(P - 1)]
-        arena = BatchedArena(self.game.engine, seats, cpuct=1.0)
+        arena = BatchedArena(self.game.engine, seats, cpuct=1.0, path=path)  # path None: BK_ARENA, default eager
         scores, _, _ = arena.play(games or self.hparams.compare_arena_games, permute=self.hparams.permute)
         return scores
 

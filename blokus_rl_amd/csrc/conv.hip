@@ -100,7 +100,9 @@ __device__ __forceinline__ void conv_run(const float* __restrict__ x, const f32x
     const int p = t * 16 + m;
     q.in = p < total_pix;
     q.b = q.in ? p / npix : 0;
-    const int rem = p - q.b * npix;
+    // a pixel past the batch (the last tile's tail, or the tile an idle wave preloads) reads pixel
+    // 0 of board 0, masked by keep = 0: with rem = p it read up to 16 pixels per wave past the end of x
+    const int rem = q.in ? p - q.b * npix : 0;
     q.py = rem / N;
     q.px = rem - q.py * N;
     return q;

@@ -66,17 +66,53 @@ constexpr int kLnRowWords = kLnP * kMaxN;   // a state's board rows: plane p, ro
 // bk_observe(states) as float values. A board whose status is not 1 (no leaf for the net: its
 // state row is stale) is the all-zero observation, as the search writes it in the planar form;
 // its state words are not loaded.
-template <int N, typename In>  // In: const float* (planes) or LnStates
+template <int N, typename In>  // In: const float* (planes), LnStates or LnRows
 __global__ __launch_bounds__(kLnThreads, 1) void k_leafnet_x3(In in,
-                                                              const h16x8* __restrict__ wstem,
-                                                              const float* __restrict__ sstem,
-                                                              const float* __restrict__ bstem,
-                                                              const h16x8* __restrict__ wt,
-                                                              const float* __restrict__ st,
-                                                              const float* __restrict__ bt,
-                                                              const float* __restrict__ bounds, int nlayers,
-                                                              LnHeads hd, float* __restrict__ xout) {
-  constexpr bool STATES = std::is_same<In, LnStates>::value;
+                                                              const h16x8* __restrict__ wstem_a,
+                                                              const float* __restrict__ sstem_a,
+                                                              const float* __restrict__ bstem_a,
+                                                              const h16x8* __restrict__ wt_a,
+                                                              const float* __restrict__ st_a,
+                                                              const float* __restrict__ bt_a,
+                                                              const float* __restrict__ bounds_a, int nlayers,
+                                                              LnHeads hd_a, float* __restrict__ xout) {
+  // ROWS (bk_leafnet_x3_rows): the STATES form on state row tree[blockIdx.x] with the row's own
+  // weight set; the *_a weight arguments are unused (null) and the operands below come from the
+  // table in `in`. The other forms take the arguments as they are.
+  constexpr bool ROWS = std::is_same<In, LnRows>::value;
+  constexpr bool STATES = std::is_same<In, LnStates>::value || ROWS;
+  const h16x8* __restrict__ wstem = wstem_a;
+  const float* __restrict__ sstem = sstem_a;
+  const float* __restrict__ bstem = bstem_a;
+  const h16x8* __restrict__ wt = wt_a;
+  const float* __restrict__ st = st_a;
+  const float* __restrict__ bt = bt_a;
+  const float* __restrict__ bounds = bounds_a;
+  LnHeads hd = hd_a;
+  size_t b = blockIdx.x;
+  if constexpr (ROWS) {
+    // workgroup-uniform, before any barrier or LDS use
+    int k;
+    const int t = ln_row_tree(in, blockIdx.x, k);
+    if (t < 0) return;
+    b = (size_t)t;
+    const LnNet nk = ln_pick(in.nets, k);
+    wstem = nk.wstem;
+    sstem = nk.sstem;
+    bstem = nk.bstem;
+    wt = nk.wt;
+    st = nk.st;
+    bt = nk.bt;
+    bounds = nk.bounds;
+    hd.wp = nk.wp;
+    hd.bp = nk.bp;
+    hd.wv = nk.wv;
+    hd.bv = nk.bv;
+    hd.w1t = nk.w1t;
+    hd.b1 = nk.b1;
+    hd.w2 = nk.w2;
+    hd.b2 = nk.b2;
+  }
   constexpr int NN = N * N, RS = ln_row(N), NG = ln_groups(N), PIX_IT = (NN + kLnThreads - 1) / kLnThreads;
   constexpr int PL = ln_plane(N);
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
@@ -88,7 +124,6 @@ __global__ __launch_bounds__(kLnThreads, 1) void k_leafnet_x3(In in,
   const int tid = threadIdx.x, l = tid & 63, n = l & 15, ks = l >> 4;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // wave-uniform
   const int oc = 16 * wave + 4 * ks;  // the lane's 4 output channels oc..oc+3 in the D fragments
-  const size_t b = blockIdx.x;
   LNSTAMP(0, __builtin_amdgcn_s_memtime());
   LNSTAMP(30, __builtin_amdgcn_s_memrealtime());
 
@@ -98,7 +133,7 @@ __global__ __launch_bounds__(kLnThreads, 1) void k_leafnet_x3(In in,
   bool live = true;
   if constexpr (STATES) {
     static_assert(kLnRowWords < kLnThreads && N <= kMaxN, "k_leafnet_x3: one state word per thread");
-    live = !in.status || in.status[b] == 1;
+    live = ROWS || !in.status || in.status[b] == 1;  // ROWS: a leaf, or the workgroup has returned
     if (live && tid <= kLnRowWords) sw = in.states[b * kStateWords + (tid < kLnRowWords ? tid : kWToMove)];
   } else {
     const float* __restrict__ ob = in + b * kStemCinX3 * NN;
@@ -664,6 +699,51 @@ int bk_leafnet_x3_states(const void* states, const int32_t* status, int B, int N
     hipLaunchKernelGGL((k_leafnet_x3<14, LnStates>), dim3(B), dim3(kLnThreads), ln_lds_bytes(14), s, in, ws, sstem, bstem,
                        wt, stower, btower, bounds, nlayers, h, out);
   return launch_check("k_leafnet_x3 (states)");
+}
+
+int bk_leafnet_x3_rows(const bk_leafnet_args* nets, int nnets, const bk_arena_rows* rows, int sim, void* stream) {
+  BK_REQUIRE(rows && nnets >= 0 && nnets <= kLnMaxNets && sim >= 0, "bk_leafnet_x3_rows: bad argument");
+  BK_REQUIRE(rows->R >= 0 && rows->T >= 0 && (rows->R == 0 || (rows->tree_of_row && rows->net_of_row && rows->sims_of_row)),
+             "bk_leafnet_x3_rows: bad row tables");
+  if (nnets == 0 || rows->R == 0) return BK_OK;
+  BK_REQUIRE(nets, "bk_leafnet_x3_rows: null net table");
+  const bk_leafnet_args& a0 = nets[0];
+  const auto a16 = [](const void* p) { return ((uintptr_t)p & 15u) == 0; };
+  for (int k = 0; k < nnets; ++k) {
+    const bk_leafnet_args& a = nets[k];
+    BK_REQUIRE(!a.obs && a.states && a.status, "bk_leafnet_x3_rows: states form only (states and status set, obs null)");
+    BK_REQUIRE(a.states == a0.states && a.status == a0.status && a.pf == a0.pf && a.vout == a0.vout && a.N == a0.N &&
+                   a.P == a0.P && a.nlayers == a0.nlayers && a.np == a0.np,
+               "bk_leafnet_x3_rows: the nets must share states, status, pf, vout, N, P, nlayers and np");
+    BK_REQUIRE(a.wstem && a.sstem && a.bstem && a.wtower && a.stower && a.btower && a.bounds && a.wp && a.bp && a.wv &&
+                   a.bv && a.w1t && a.b1 && a.w2 && a.b2 && a.pf && a.vout,
+               "bk_leafnet_x3_rows: null net operand");
+    BK_REQUIRE(a16(a.wstem) && a16(a.wtower) && a16(a.sstem) && a16(a.bstem) && a16(a.stower) && a16(a.btower) &&
+                   a16(a.wp) && a16(a.wv),
+               "bk_leafnet_x3_rows: 16-byte aligned buffers");
+  }
+  BK_REQUIRE(a0.nlayers >= 1, "bk_leafnet_x3_rows: at least one tower conv");
+  BK_REQUIRE(((uintptr_t)a0.states & 3u) == 0, "bk_leafnet_x3_rows: states must be 4-byte aligned");
+  if (a0.np) return bk::leafnet_np_rows(nets, nnets, rows, sim, stream);
+  BK_REQUIRE(a0.P == kLnP, "bk_leafnet_x3_rows: the classic form takes P = 4 (np = 0)");
+  BK_REQUIRE(bk_leafnet_x3_supported(a0.N), "bk_leafnet_x3_rows: N must be 14 or 20 (np = 0)");
+  {
+    const void* fns[2] = {(const void*)k_leafnet_x3<14, LnRows>, (const void*)k_leafnet_x3<20, LnRows>};
+    if (set_max_dynamic_lds(fns, 2, ln_lds_bytes(20)) != BK_OK) return BK_EHIP;
+  }
+  const LnRows in = ln_rows_of(nets, nnets, rows, sim);
+  const LnHeads h{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, a0.P, a0.pf, a0.vout};
+  hipStream_t s = (hipStream_t)stream;
+  const h16x8* nw = nullptr;
+  const float* nf = nullptr;
+  float* out = nullptr;
+  if (a0.N == 20)
+    hipLaunchKernelGGL((k_leafnet_x3<20, LnRows>), dim3(rows->R), dim3(kLnThreads), ln_lds_bytes(20), s, in, nw, nf, nf,
+                       nw, nf, nf, nf, a0.nlayers, h, out);
+  else
+    hipLaunchKernelGGL((k_leafnet_x3<14, LnRows>), dim3(rows->R), dim3(kLnThreads), ln_lds_bytes(14), s, in, nw, nf, nf,
+                       nw, nf, nf, nf, a0.nlayers, h, out);
+  return launch_check("k_leafnet_x3 (rows)");
 }
 
 }  // extern "C"

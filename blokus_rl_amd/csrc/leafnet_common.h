@@ -6,6 +6,9 @@
 #include "ctx.h"
 
 namespace bk {
+// bk_leafnet_x3_rows for a net table of the np form (leafnet_np.hip); the table is validated
+int leafnet_np_rows(const bk_leafnet_args* nets, int nnets, const bk_arena_rows* rows, int sim, void* stream);
+
 namespace {
 
 using h16x8 = _Float16 __attribute__((ext_vector_type(8)));
@@ -392,6 +395,76 @@ struct LnHeads {
   float* pf;
   float* v;
 };
+
+// The rows form of the packed-state input (bk_leafnet_x3_rows): workgroup r evaluates the state
+// row tree[r] with the weight set nets[net[r]], or returns at once when the row is not live at
+// `sim`, its seat is uninformed or its tree has no leaf for the net. The weight sets travel as
+// kernel arguments and are picked by a wave-uniform index (scalar selects: the MFMA loop sees the
+// same scalar pointers as the single-net kernels).
+constexpr int kLnMaxNets = BK_ARENA_MAX_NETS;
+struct LnNet {
+  const h16x8* wstem;
+  const float *sstem, *bstem;
+  const h16x8* wt;
+  const float *st, *bt, *bounds;
+  const float *wp, *bp, *wv, *bv, *w1t, *b1, *w2, *b2;
+};
+struct LnRows {
+  const uint32_t* states;
+  const int32_t* status;
+  const int32_t *tree, *net, *sims;
+  int sim, nnets, ntrees;
+  LnNet nets[kLnMaxNets];
+};
+__device__ __forceinline__ LnNet ln_pick(const LnNet (&n)[kLnMaxNets], int k) {
+  LnNet o;
+#define BK_LN_PICK(f) o.f = k == 0 ? n[0].f : k == 1 ? n[1].f : k == 2 ? n[2].f : n[3].f
+  BK_LN_PICK(wstem);
+  BK_LN_PICK(sstem);
+  BK_LN_PICK(bstem);
+  BK_LN_PICK(wt);
+  BK_LN_PICK(st);
+  BK_LN_PICK(bt);
+  BK_LN_PICK(bounds);
+  BK_LN_PICK(wp);
+  BK_LN_PICK(bp);
+  BK_LN_PICK(wv);
+  BK_LN_PICK(bv);
+  BK_LN_PICK(w1t);
+  BK_LN_PICK(b1);
+  BK_LN_PICK(w2);
+  BK_LN_PICK(b2);
+#undef BK_LN_PICK
+  return o;
+}
+// the kernel's table from the C-ABI's (validated by bk_leafnet_x3_rows)
+inline LnRows ln_rows_of(const bk_leafnet_args* nets, int nnets, const bk_arena_rows* rows, int sim) {
+  LnRows in{};
+  in.states = reinterpret_cast<const uint32_t*>(nets[0].states);
+  in.status = nets[0].status;
+  in.tree = rows->tree_of_row;
+  in.net = rows->net_of_row;
+  in.sims = rows->sims_of_row;
+  in.sim = sim;
+  in.nnets = nnets;
+  in.ntrees = rows->T;
+  for (int k = 0; k < nnets; ++k) {
+    const bk_leafnet_args& a = nets[k];
+    in.nets[k] = LnNet{reinterpret_cast<const h16x8*>(a.wstem), a.sstem, a.bstem,
+                       reinterpret_cast<const h16x8*>(a.wtower), a.stower, a.btower, a.bounds,
+                       a.wp, a.bp, a.wv, a.bv, a.w1t, a.b1, a.w2, a.b2};
+  }
+  return in;
+}
+// the row's tree and weight set, or -1 (workgroup-uniform) when the row has nothing to evaluate
+__device__ __forceinline__ int ln_row_tree(const LnRows& in, int r, int& k) {
+  const int t = __builtin_amdgcn_readfirstlane(in.tree[r]);
+  k = -1;
+  if (t < 0 || t >= in.ntrees || in.sim >= __builtin_amdgcn_readfirstlane(in.sims[r])) return -1;
+  k = __builtin_amdgcn_readfirstlane(in.net[r]);
+  if (k < 0 || k >= in.nnets) return -1;
+  return __builtin_amdgcn_readfirstlane(in.status[t]) == 1 ? t : -1;
+}
 
 }  // namespace
 }  // namespace bk

@@ -125,17 +125,52 @@ __device__ constexpr NpPixMap<N, Q> kNpPixMap{};
 
 constexpr int kNpRowStride = kMaxP * kMaxN + 1;  // a board's staged row words, to_move last
 
-template <int N, int Q, typename In>  // In: const float* (planes [B][2P][N][N]) or NpStates
-__global__ __launch_bounds__(kLnThreads, 1) void k_leafnet_np(In in, int B, const h16x8* __restrict__ wstem,
-                                                              const float* __restrict__ sstem,
-                                                              const float* __restrict__ bstem,
-                                                              const h16x8* __restrict__ wt,
-                                                              const float* __restrict__ st,
-                                                              const float* __restrict__ bt,
-                                                              const float* __restrict__ bounds, int nlayers,
-                                                              LnHeads hd, float* __restrict__ xout) {
+template <int N, int Q, typename In>  // In: const float* (planes [B][2P][N][N]), NpStates or LnRows (Q = 1)
+__global__ __launch_bounds__(kLnThreads, 1) void k_leafnet_np(In in, int B, const h16x8* __restrict__ wstem_a,
+                                                              const float* __restrict__ sstem_a,
+                                                              const float* __restrict__ bstem_a,
+                                                              const h16x8* __restrict__ wt_a,
+                                                              const float* __restrict__ st_a,
+                                                              const float* __restrict__ bt_a,
+                                                              const float* __restrict__ bounds_a, int nlayers,
+                                                              LnHeads hd_a, float* __restrict__ xout) {
+  // ROWS (bk_leafnet_x3_rows): the STATES form on state row tree[blockIdx.x] with the row's own
+  // weight set, as in k_leafnet_x3; the *_a weight arguments are unused (null) then
+  constexpr bool ROWS = std::is_same<In, LnRows>::value;
+  static_assert(!ROWS || Q == 1, "k_leafnet_np: rows of one workgroup could belong to different nets");
+  const h16x8* __restrict__ wstem = wstem_a;
+  const float* __restrict__ sstem = sstem_a;
+  const float* __restrict__ bstem = bstem_a;
+  const h16x8* __restrict__ wt = wt_a;
+  const float* __restrict__ st = st_a;
+  const float* __restrict__ bt = bt_a;
+  const float* __restrict__ bounds = bounds_a;
+  LnHeads hd = hd_a;
+  int row_tree = 0;
+  if constexpr (ROWS) {
+    // workgroup-uniform, before any barrier or LDS use
+    int k;
+    row_tree = ln_row_tree(in, blockIdx.x, k);
+    if (row_tree < 0) return;
+    const LnNet nk = ln_pick(in.nets, k);
+    wstem = nk.wstem;
+    sstem = nk.sstem;
+    bstem = nk.bstem;
+    wt = nk.wt;
+    st = nk.st;
+    bt = nk.bt;
+    bounds = nk.bounds;
+    hd.wp = nk.wp;
+    hd.bp = nk.bp;
+    hd.wv = nk.wv;
+    hd.bv = nk.bv;
+    hd.w1t = nk.w1t;
+    hd.b1 = nk.b1;
+    hd.w2 = nk.w2;
+    hd.b2 = nk.b2;
+  }
   using G = NpGeo<N, Q>;
-  constexpr bool STATES = std::is_same<In, NpStates>::value;
+  constexpr bool STATES = std::is_same<In, NpStates>::value || ROWS;
   constexpr int NN = G::NN, NPIX = G::NPIX, RS = G::RS, NG = G::NG, PL = G::PL, X0L = G::X0L;
   constexpr int PIX_IT = (NPIX + kLnThreads - 1) / kLnThreads;
   constexpr int QX = Q == 4 ? Q + 1 : Q;
@@ -148,8 +183,8 @@ __global__ __launch_bounds__(kLnThreads, 1) void k_leafnet_np(In in, int B, cons
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int oc = 16 * wave + 4 * ks;
   const int P = hd.P;
-  const int b0 = blockIdx.x * Q;                // the workgroup's boards b0 .. b0 + nb - 1
-  const int nb = B - b0 < Q ? B - b0 : Q;       // a tail workgroup: boards nb.. are all-zero, never loaded or stored
+  const int b0 = ROWS ? row_tree : blockIdx.x * Q;  // the workgroup's boards b0 .. b0 + nb - 1 (ROWS: the row's tree)
+  const int nb = ROWS ? 1 : (B - b0 < Q ? B - b0 : Q);  // a tail workgroup: boards nb.. are all-zero, never loaded or stored
 
   // the observation loads first (their latency under the halo zeroing below)
   float xin[STATES ? 1 : PIX_IT][kStemCinX3];
@@ -162,7 +197,8 @@ __global__ __launch_bounds__(kLnThreads, 1) void k_leafnet_np(In in, int B, cons
     for (int it = 0; it < SW_IT; ++it) {
       const int i = tid + it * kLnThreads;
       const int q = Q == 1 ? 0 : i / (RW + 1), k = i - q * (RW + 1);
-      slive[it] = i < Q * (RW + 1) && q < nb && (!in.status || in.status[b0 + q] == 1);
+      // ROWS: a leaf, or the workgroup has returned
+      slive[it] = i < Q * (RW + 1) && q < nb && (ROWS || !in.status || in.status[b0 + q] == 1);
       sw[it] = slive[it] ? in.states[(size_t)(b0 + q) * kStateWords + (k < RW ? k : kWToMove)] : 0u;
     }
   } else {
@@ -682,6 +718,24 @@ int np_dispatch(In in, int B, int N, int Q, const h16x8* ws, const float* sstem,
 }
 
 }  // namespace
+
+// bk_leafnet_x3_rows on the np form: one board per workgroup whatever np's boards_per_wg says (the
+// rows of a four-board workgroup could belong to different nets); a board's outputs do not depend
+// on the form, so they are bitwise those of bk_leafnet_x3_np_states
+int leafnet_np_rows(const bk_leafnet_args* nets, int nnets, const bk_arena_rows* rows, int sim, void* stream) {
+  const bk_leafnet_args& a0 = nets[0];
+  BK_REQUIRE(a0.N == 7 || a0.N == 14 || a0.N == 20, "bk_leafnet_x3_rows: N must be 7, 14 or 20 (np form)");
+  BK_REQUIRE(a0.P >= 2 && a0.P <= kMaxP, "bk_leafnet_x3_rows: P must be 2, 3 or 4 (np form)");
+  const LnRows in = ln_rows_of(nets, nnets, rows, sim);
+  const LnHeads h{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, a0.P, a0.pf, a0.vout};
+  const h16x8* nw = nullptr;
+  const float* nf = nullptr;
+  hipStream_t s = (hipStream_t)stream;
+  // B = R workgroups of one board each (the kernel takes its board from the row table)
+  if (a0.N == 7) return np_launch<7, 1, LnRows>(in, rows->R, nw, nf, nf, nw, nf, nf, nf, a0.nlayers, h, nullptr, s);
+  if (a0.N == 14) return np_launch<14, 1, LnRows>(in, rows->R, nw, nf, nf, nw, nf, nf, nf, a0.nlayers, h, nullptr, s);
+  return np_launch<20, 1, LnRows>(in, rows->R, nw, nf, nf, nw, nf, nf, nf, a0.nlayers, h, nullptr, s);
+}
 }  // namespace bk
 
 using namespace bk;

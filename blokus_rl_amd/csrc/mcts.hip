@@ -96,6 +96,60 @@ __device__ __forceinline__ void wg_store_handoff() {
   asm volatile("buffer_inv sc0" ::: "memory");
 }
 constexpr int kStepWaves = 16;  // waves per tree in k_leaf_step: the logit gather's memory parallelism
+// An uninformed seat's leaf (the rows entries, net_of_row = -1): leaf_logits_tree with every
+// logit 0 and no weight read (the ids compacted the same way, into leaf_ids).
+__device__ __forceinline__ void leaf_zero_logits_tree(const DevPreset& dp, const DevMcts& m, int t,
+                                                      const float* __restrict__ feat, int64_t ldf, int F,
+                                                      uint32_t* lds) {
+  const int K = leaf_logits_prologue(dp, m, t, 0, feat, ldf, F, lds);
+  if (K < 0 || K > kLeafCap) return;
+  const int32_t* ids = reinterpret_cast<const int32_t*>(lds + dp.W32pad);
+  for (int j = threadIdx.x; j < K; j += blockDim.x) {
+    m.leaf_ids[(size_t)t * kLeafCap + j] = ids[j];
+    m.leaf_logit[(size_t)t * kLeafCap + j] = 0.0f;
+  }
+}
+// k_leaf_step's work on tree t. ROWS (k_leaf_step_rows): roots is indexed by root_row, and
+// `uninformed` (workgroup-uniform) takes zero logits and, with values null, zero values.
+template <bool ROWS>
+__device__ __forceinline__ void leaf_step_body(const DevPreset& dp, const DevMcts& m, const int t,
+                                               const float* __restrict__ feat, int64_t ldf, int F,
+                                               const float* __restrict__ W, const float* __restrict__ bias,
+                                               const float* __restrict__ values, int do_select,
+                                               const uint32_t* __restrict__ roots,
+                                               const int32_t* __restrict__ active, double cpuct,
+                                               int32_t* __restrict__ status_out, float* __restrict__ obs,
+                                               uint64_t* __restrict__ mask_out, bool uninformed, int root_row) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+  __shared__ int status_sh;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+#ifdef BK_STAMPS
+#define BK_STEP_STAMP(i) \
+  do { if (do_select && threadIdx.x == 0 && t < 4096) g_step_stamps[t][i] = __builtin_amdgcn_s_memtime(); } while (0)
+#else
+#define BK_STEP_STAMP(i) do { } while (0)
+#endif
+  BK_STEP_STAMP(0);
+  if (ROWS && uninformed)
+    leaf_zero_logits_tree(dp, m, t, feat, ldf, F, lds);
+  else
+    leaf_logits_tree<kLeafR>(dp, m, t, 0, 1, feat, ldf, F, W, bias, lds);
+  wg_store_handoff();
+  BK_STEP_STAMP(1);
+  if (wave == 0) expand_tree<ROWS>(dp, m, t, nullptr, values, 2, lds);
+  wg_store_handoff();
+  BK_STEP_STAMP(2);
+  if (!do_select) return;
+  if (wave == 0) {
+    const int st = select_descend<ROWS>(dp, m, t, roots, active, cpuct, status_out, lds, 0, nullptr, 1e-6, root_row);
+    if (lane_id() == 0) status_sh = st;
+  }
+  __syncthreads();
+  BK_STEP_STAMP(3);
+  select_leaf<kStepWaves>(dp, m, t, status_sh, obs, mask_out, lds, wave);
+  BK_STEP_STAMP(4);
+#undef BK_STEP_STAMP
+}
 __global__ __launch_bounds__(64 * kStepWaves) void k_leaf_step(DevPreset dp, DevMcts m, const float* __restrict__ feat,
                                                                  int64_t ldf, int F, const float* __restrict__ W,
                                                                  const float* __restrict__ bias,
@@ -105,33 +159,8 @@ __global__ __launch_bounds__(64 * kStepWaves) void k_leaf_step(DevPreset dp, Dev
                                                                  int32_t* __restrict__ status_out,
                                                                  float* __restrict__ obs,
                                                                  uint64_t* __restrict__ mask_out, int t0) {
-  extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
-  __shared__ int status_sh;
-  const int t = t0 + blockIdx.x;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-#ifdef BK_STAMPS
-#define BK_STEP_STAMP(i) \
-  do { if (do_select && threadIdx.x == 0 && t < 4096) g_step_stamps[t][i] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define BK_STEP_STAMP(i) do { } while (0)
-#endif
-  BK_STEP_STAMP(0);
-  leaf_logits_tree<kLeafR>(dp, m, t, 0, 1, feat, ldf, F, W, bias, lds);
-  wg_store_handoff();
-  BK_STEP_STAMP(1);
-  if (wave == 0) expand_tree(dp, m, t, nullptr, values, 2, lds);
-  wg_store_handoff();
-  BK_STEP_STAMP(2);
-  if (!do_select) return;
-  if (wave == 0) {
-    const int st = select_descend(dp, m, t, roots, active, cpuct, status_out, lds);
-    if (lane_id() == 0) status_sh = st;
-  }
-  __syncthreads();
-  BK_STEP_STAMP(3);
-  select_leaf<kStepWaves>(dp, m, t, status_sh, obs, mask_out, lds, wave);
-  BK_STEP_STAMP(4);
-#undef BK_STEP_STAMP
+  leaf_step_body<false>(dp, m, t0 + blockIdx.x, feat, ldf, F, W, bias, values, do_select, roots, active, cpuct,
+                        status_out, obs, mask_out, false, -1);
 }
 
 // k_leaf_step with the expansion overlapped (the default; BK_STEP_OVERLAP=0 keeps k_leaf_step).
@@ -146,20 +175,21 @@ __global__ __launch_bounds__(64 * kStepWaves) void k_leaf_step(DevPreset dp, Dev
 // launches; what goes is the wait of the expansion and descent for the slowest logit wave.
 // lds = [W32pad mask | kLeafCap ids | F features | kLeafCap logits] then, at sel_off, the
 // descent's [state | 2 kMaxN | W32pad].
-__global__ __launch_bounds__(64 * kStepWaves) void k_leaf_step_ov(DevPreset dp, DevMcts m, const float* __restrict__ feat,
-                                                                    int64_t ldf, int F, const float* __restrict__ W,
-                                                                    const float* __restrict__ bias,
-                                                                    const float* __restrict__ values, int do_select,
-                                                                    const uint32_t* __restrict__ roots,
-                                                                    const int32_t* __restrict__ active, double cpuct,
-                                                                    int32_t* __restrict__ status_out,
-                                                                    float* __restrict__ obs,
-                                                                    uint64_t* __restrict__ mask_out, int sel_off,
-                                                                    int skipz, int t0) {
+// ROWS (k_leaf_step_ov_rows): roots is indexed by root_row; `uninformed` (workgroup-uniform): the
+// logit waves store zeros instead of the dot products, and values is null (zero values).
+template <bool ROWS>
+__device__ __forceinline__ void leaf_step_ov_body(const DevPreset& dp, const DevMcts& m, const int t,
+                                                  const float* __restrict__ feat, int64_t ldf, int F,
+                                                  const float* __restrict__ W, const float* __restrict__ bias,
+                                                  const float* __restrict__ values, int do_select,
+                                                  const uint32_t* __restrict__ roots,
+                                                  const int32_t* __restrict__ active, double cpuct,
+                                                  int32_t* __restrict__ status_out, float* __restrict__ obs,
+                                                  uint64_t* __restrict__ mask_out, int sel_off, int skipz,
+                                                  bool uninformed, int root_row) {
   extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
   __shared__ int status_sh, status0_sh;
   __shared__ StepExpand sx;
-  const int t = t0 + blockIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
 #ifdef BK_STAMPS
   // diag: 0 start, 1 the new node's entry published (wave 1), 2 wave 0 backup done, 3 wave 0 descent done, 4 the last logit
@@ -215,7 +245,7 @@ __global__ __launch_bounds__(64 * kStepWaves) void k_leaf_step_ov(DevPreset dp, 
   uint32_t* lsel = lds + sel_off;
   uint32_t* m32 = lsel + kStateWords + 2 * kMaxN;
   if (wave == 0) {
-    const StepHead h = backup_first(m, t, dp.P, values, status0);
+    const StepHead h = backup_first<ROWS>(m, t, dp.P, values, status0);
     if (h.status == 1) {
       // wave 1 adds the new node once the leaf's ids are compacted
       if (lane_id() == 0) {
@@ -239,8 +269,8 @@ __global__ __launch_bounds__(64 * kStepWaves) void k_leaf_step_ov(DevPreset dp, 
       pend[0] = &sx.ready;
       pend[1] = &sx.pready;
       pend[2] = &sx.err;
-      const int st = select_descend(dp, m, t, roots, active, cpuct, status_out, lsel, h.key,
-                                    h.status == 1 ? pend : nullptr);
+      const int st = select_descend<ROWS>(dp, m, t, roots, active, cpuct, status_out, lsel, h.key,
+                                          h.status == 1 ? pend : nullptr, 1e-6, root_row);
       if (st == 1)
         for (int i = lane_id(); i < dp.W32pad / 4; i += kWave) reinterpret_cast<uint4*>(m32)[i] = make_uint4(0u, 0u, 0u, 0u);
       if (lane_id() == 0) {
@@ -254,7 +284,11 @@ __global__ __launch_bounds__(64 * kStepWaves) void k_leaf_step_ov(DevPreset dp, 
     }
   }
   if (wave > 0 && K >= 0 && K <= kLeafCap) {
-    leaf_logits_dots<kLeafR>(dp, 0, K, wave - 1, kStepWaves - 1, W, bias, F, lds, nullptr, lg, skipz);
+    if (ROWS && uninformed) {
+      for (int j = (wave - 1) * kWave + lane_id(); j < K; j += (kStepWaves - 1) * kWave) lg[j] = 0.0f;
+    } else {
+      leaf_logits_dots<kLeafR>(dp, 0, K, wave - 1, kStepWaves - 1, W, bias, F, lds, nullptr, lg, skipz);
+    }
     int done = 0;
     if (lane_id() == 0) done = __hip_atomic_fetch_add(&sx.done, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_WORKGROUP);
     done = readlane_i(done, 0);
@@ -293,6 +327,129 @@ __global__ __launch_bounds__(64 * kStepWaves) void k_leaf_step_ov(DevPreset dp, 
   select_leaf<kStepWaves, true, false>(dp, m, t, status_sh, obs, mask_out, lsel, wave);
   if (wave == 0) BK_OV_STAMP(7);
 #undef BK_OV_STAMP
+}
+__global__ __launch_bounds__(64 * kStepWaves) void k_leaf_step_ov(DevPreset dp, DevMcts m, const float* __restrict__ feat,
+                                                                    int64_t ldf, int F, const float* __restrict__ W,
+                                                                    const float* __restrict__ bias,
+                                                                    const float* __restrict__ values, int do_select,
+                                                                    const uint32_t* __restrict__ roots,
+                                                                    const int32_t* __restrict__ active, double cpuct,
+                                                                    int32_t* __restrict__ status_out,
+                                                                    float* __restrict__ obs,
+                                                                    uint64_t* __restrict__ mask_out, int sel_off,
+                                                                    int skipz, int t0) {
+  leaf_step_ov_body<false>(dp, m, t0 + blockIdx.x, feat, ldf, F, W, bias, values, do_select, roots, active, cpuct,
+                           status_out, obs, mask_out, sel_off, skipz, false, -1);
+}
+
+// ---- the arena's rows entries (bk_mcts_select_rows, bk_mcts_leaf_step_rows, bk_arena_move): one
+// workgroup per row (game), tree t = tree_of_row[blockIdx.x]; a row that is not live at `sim`
+// returns before it touches anything (workgroup-uniform, before any barrier or LDS use).
+struct RowTabs {
+  const int32_t *tree, *net, *sims;
+};
+struct RowHeads {
+  const float* W[BK_ARENA_MAX_NETS];
+  const float* bias[BK_ARENA_MAX_NETS];
+  int n;
+};
+// the row's tree, or -1 when the row is not live at sim; budget = its simulations this ply
+__device__ __forceinline__ int row_live_tree(const RowTabs& rows, int r, int sim, int& budget) {
+  const int t = __builtin_amdgcn_readfirstlane(rows.tree[r]);
+  budget = 0;
+  if (t < 0) return -1;
+  budget = __builtin_amdgcn_readfirstlane(rows.sims[r]);
+  return sim < budget ? t : -1;
+}
+// the row's policy Linear by a wave-uniform index (scalar selects); false: no such net in the table
+__device__ __forceinline__ bool row_head(const RowTabs& rows, const RowHeads& hd, int r, const float*& W,
+                                         const float*& bias, bool& uninformed) {
+  const int k = __builtin_amdgcn_readfirstlane(rows.net[r]);
+  uninformed = k < 0;
+  W = k == 0 ? hd.W[0] : k == 1 ? hd.W[1] : k == 2 ? hd.W[2] : k == 3 ? hd.W[3] : nullptr;
+  bias = k == 0 ? hd.bias[0] : k == 1 ? hd.bias[1] : k == 2 ? hd.bias[2] : k == 3 ? hd.bias[3] : nullptr;
+  return k < hd.n;
+}
+
+__global__ __launch_bounds__(64 * kSelectWaves) void k_select_rows(DevPreset dp, DevMcts m, RowTabs rows,
+                                                                   const uint32_t* __restrict__ roots, double cpuct,
+                                                                   int32_t* __restrict__ status_out) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+  __shared__ int status_sh;
+  int budget;
+  const int t = row_live_tree(rows, blockIdx.x, 0, budget);
+  if (t < 0 || t >= m.T) return;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (wave == 0) {
+    const int st = select_descend<true>(dp, m, t, roots, nullptr, cpuct, status_out, lds, 0, nullptr, 1e-6, (int)blockIdx.x);
+    if (lane_id() == 0) status_sh = st;
+  }
+  __syncthreads();
+  select_leaf<kSelectWaves>(dp, m, t, status_sh, nullptr, nullptr, lds, wave);
+}
+
+__global__ __launch_bounds__(64 * kStepWaves) void k_leaf_step_rows(DevPreset dp, DevMcts m, RowTabs rows, int sim,
+                                                                      const float* __restrict__ feat, int64_t ldf, int F,
+                                                                      RowHeads heads, const float* __restrict__ values,
+                                                                      int do_select, const uint32_t* __restrict__ roots,
+                                                                      double cpuct, int32_t* __restrict__ status_out) {
+  int budget;
+  const int t = row_live_tree(rows, blockIdx.x, sim, budget);
+  if (t < 0 || t >= m.T) return;
+  const float *W, *bias;
+  bool uninformed;
+  if (!row_head(rows, heads, blockIdx.x, W, bias, uninformed)) return;
+  leaf_step_body<true>(dp, m, t, feat, ldf, F, W, bias, uninformed ? nullptr : values,
+                       do_select && sim + 1 < budget, roots, nullptr, cpuct, status_out, nullptr, nullptr, uninformed,
+                       (int)blockIdx.x);
+}
+
+__global__ __launch_bounds__(64 * kStepWaves) void k_leaf_step_ov_rows(DevPreset dp, DevMcts m, RowTabs rows, int sim,
+                                                                         const float* __restrict__ feat, int64_t ldf,
+                                                                         int F, RowHeads heads,
+                                                                         const float* __restrict__ values, int do_select,
+                                                                         const uint32_t* __restrict__ roots, double cpuct,
+                                                                         int32_t* __restrict__ status_out, int sel_off,
+                                                                         int skipz) {
+  int budget;
+  const int t = row_live_tree(rows, blockIdx.x, sim, budget);
+  if (t < 0 || t >= m.T) return;
+  const float *W, *bias;
+  bool uninformed;
+  if (!row_head(rows, heads, blockIdx.x, W, bias, uninformed)) return;
+  leaf_step_ov_body<true>(dp, m, t, feat, ldf, F, W, bias, uninformed ? nullptr : values,
+                          do_select && sim + 1 < budget, roots, nullptr, cpuct, status_out, nullptr, nullptr, sel_off,
+                          skipz, uninformed, (int)blockIdx.x);
+}
+
+// The T = 0 move of every live row: k_root's one-hot rule (the first child with maximal N) read
+// straight from the tree, no [T][cap] rows.
+__global__ __launch_bounds__(64) void k_arena_move(DevMcts m, RowTabs rows, const uint32_t* __restrict__ roots,
+                                                   int32_t* __restrict__ action) {
+  const int r = blockIdx.x, l = lane_id();
+  const int t = __builtin_amdgcn_readfirstlane(rows.tree[r]);
+  if (t < 0 || t >= m.T) {
+    if (l == 0) action[r] = -1;
+    return;
+  }
+  const uint64_t key = table_key(roots + (size_t)r * kStateWords);
+  int64_t off;
+  int K;
+  if (!table_find(m, t, key, off, K, nullptr)) {
+    if (l == 0) {
+      action[r] = -1;
+      atomicOr(&m.counters[kCtrErr], (unsigned long long)kErrMissingRoot);
+    }
+    return;
+  }
+  double best = -1.0;
+  int bi = 0x7fffffff;
+  for (int i = l; i < K; i += kWave) {
+    const double v = (double)m.ch_N[off + i];
+    if (v > best) { best = v; bi = i; }
+  }
+  wave_argmax(best, bi);
+  if (l == 0) action[r] = K > 0 ? m.ch_id[off + bi] : -1;
 }
 
 __device__ __forceinline__ double raise_visits(uint32_t n, double e) {
@@ -579,6 +736,102 @@ int bk_mcts_leaf_step_range(bk_mcts* m, int t0, int n, const float* feat, int64_
              "bk_mcts_leaf_step_range: need 0 <= t0, 0 <= n, t0 + n <= T");
   return leaf_step_launch(m, t0, n, feat, ldf, F, W, bias, values, do_select, roots, active, cpuct, leaf_status, obs,
                           leaf_mask, stream);
+}
+
+// ---- the arena's rows entries
+static int rows_check(const bk_arena_rows* rows, const char* what) {
+  if (!rows || rows->R < 0 || rows->T < 0 || (rows->R > 0 && !(rows->tree_of_row && rows->net_of_row && rows->sims_of_row))) {
+    bk::set_error(what);
+    return BK_EINVAL;
+  }
+  return BK_OK;
+}
+static RowTabs row_tabs(const bk_arena_rows* rows) {
+  return RowTabs{rows->tree_of_row, rows->net_of_row, rows->sims_of_row};
+}
+
+int bk_mcts_select_rows(bk_mcts* m, const bk_arena_rows* rows, const void* roots, double cpuct, int32_t* leaf_status,
+                        void* stream) {
+  BK_REQUIRE(m && roots && leaf_status, "bk_mcts_select_rows: bad argument");
+  if (int rc = rows_check(rows, "bk_mcts_select_rows: bad row tables")) return rc;
+  if (rows->R == 0) return BK_OK;
+  const DevPreset& dp = m->ctx->dp;
+  const size_t lds = sizeof(uint32_t) * (size_t)(kStateWords + 2 * kMaxN + dp.W32pad);
+  hipLaunchKernelGGL(k_select_rows, dim3(rows->R), dim3(kWave * kSelectWaves), lds, (hipStream_t)stream, dp, m->d,
+                     row_tabs(rows), (const uint32_t*)roots, cpuct, leaf_status);
+  return launch_check("k_select_rows");
+}
+
+int bk_mcts_leaf_step_rows(bk_mcts* m, const bk_arena_rows* rows, int sim, const float* feat, int64_t ldf, int F,
+                           const bk_arena_heads* heads, const float* values, int do_select, const void* roots,
+                           double cpuct, int32_t* leaf_status, void* stream) {
+  BK_REQUIRE(m && feat && values && heads && sim >= 0 && F > 0 && F <= kMaxFeat && ldf >= F,
+             "bk_mcts_leaf_step_rows: bad argument");
+  BK_REQUIRE(heads->n >= 0 && heads->n <= BK_ARENA_MAX_NETS, "bk_mcts_leaf_step_rows: at most 4 nets");
+  BK_REQUIRE(!do_select || (roots && leaf_status), "bk_mcts_leaf_step_rows: bad argument: select outputs");
+  if (int rc = rows_check(rows, "bk_mcts_leaf_step_rows: bad row tables")) return rc;
+  RowHeads hd{};
+  hd.n = heads->n;
+  for (int k = 0; k < heads->n; ++k) {
+    BK_REQUIRE(heads->W[k] && heads->bias[k], "bk_mcts_leaf_step_rows: null policy head");
+    BK_REQUIRE(((uintptr_t)heads->W[k] & 15u) == 0 || (F & 3) != 0, "bk_mcts_leaf_step_rows: W must be 16-byte aligned");
+    hd.W[k] = heads->W[k];
+    hd.bias[k] = heads->bias[k];
+  }
+  if (rows->R == 0) return BK_OK;
+  const DevPreset& dp = m->ctx->dp;
+  const char* ov = getenv("BK_STEP_OVERLAP");  // read per call (graph capture reads it once)
+  const int overlap = ov ? atoi(ov) : 1;
+  if (overlap) {
+    const int sel_off = (int)(((size_t)dp.W32pad + 2 * kLeafCap + F + 3) & ~(size_t)3);
+    const size_t words = (size_t)sel_off + kStateWords + 2 * kMaxN + dp.W32pad;
+    const char* sz = getenv("BK_LEAF_SKIP0");
+    const int skipz = sz ? atoi(sz) : 1;
+    hipLaunchKernelGGL(k_leaf_step_ov_rows, dim3(rows->R), dim3(kWave * kStepWaves), sizeof(uint32_t) * words,
+                       (hipStream_t)stream, dp, m->d, row_tabs(rows), sim, feat, ldf, F, hd, values, do_select,
+                       (const uint32_t*)roots, cpuct, leaf_status, sel_off, skipz);
+    return launch_check("k_leaf_step_ov_rows");
+  }
+  size_t words = (size_t)dp.W32pad + kLeafCap + F;                               // leaf logits
+  words = std::max(words, (size_t)dp.W32pad + kExpandLdsIds);                    // expand
+  words = std::max(words, (size_t)(kStateWords + 2 * kMaxN + dp.W32pad));       // select
+  hipLaunchKernelGGL(k_leaf_step_rows, dim3(rows->R), dim3(kWave * kStepWaves), sizeof(uint32_t) * words,
+                     (hipStream_t)stream, dp, m->d, row_tabs(rows), sim, feat, ldf, F, hd, values, do_select,
+                     (const uint32_t*)roots, cpuct, leaf_status);
+  return launch_check("k_leaf_step_rows");
+}
+
+int bk_arena_move(bk_mcts* m, const bk_arena_rows* rows, const void* roots, int32_t* action, void* stream) {
+  BK_REQUIRE(m && roots && action, "bk_arena_move: bad argument");
+  if (int rc = rows_check(rows, "bk_arena_move: bad row tables")) return rc;
+  if (rows->R == 0) return BK_OK;
+  hipLaunchKernelGGL(k_arena_move, dim3(rows->R), dim3(kWave), 0, (hipStream_t)stream, m->d, row_tabs(rows),
+                     (const uint32_t*)roots, action);
+  return launch_check("k_arena_move");
+}
+
+int bk_arena_sims(bk_mcts* m, const bk_leafnet_args* nets, int nnets, const bk_arena_rows* rows, int max_sims,
+                  const bk_arena_heads* heads, const float* pf, const float* vout, const void* roots, double cpuct,
+                  int32_t* leaf_status, void* stream) {
+  BK_REQUIRE(m && heads && pf && vout && roots && leaf_status && max_sims >= 0 && nnets >= 0 &&
+                 nnets <= BK_ARENA_MAX_NETS && heads->n == nnets,
+             "bk_arena_sims: bad argument (one policy head per net)");
+  BK_REQUIRE(nnets == 0 || (nets && nets[0].pf == pf && nets[0].vout == vout && nets[0].status == leaf_status),
+             "bk_arena_sims: the nets must write pf / vout and read the status the search writes");
+  if (int rc = rows_check(rows, "bk_arena_sims: bad row tables")) return rc;
+  const int F = 2 * m->ctx->dp.N * m->ctx->dp.N;
+  BK_REQUIRE(nnets == 0 || (nets[0].N == m->ctx->dp.N && nets[0].P == m->ctx->dp.P),
+             "bk_arena_sims: the nets' board and players must be the engine's");
+  if (max_sims == 0) return BK_OK;
+  // one stream, no forks: select, then per simulation the multi-net leaf launch and the step
+  int rc = bk_mcts_select_rows(m, rows, roots, cpuct, leaf_status, stream);
+  for (int s = 0; !rc && s < max_sims; ++s) {
+    rc = bk_leafnet_x3_rows(nets, nnets, rows, s, stream);
+    if (!rc)
+      rc = bk_mcts_leaf_step_rows(m, rows, s, pf, F, F, heads, vout, s + 1 < max_sims, roots, cpuct, leaf_status,
+                                  stream);
+  }
+  return rc;
 }
 
 // The streams and events of bk_mcts_sims_pipelined, once per object.

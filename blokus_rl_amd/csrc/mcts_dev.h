@@ -217,11 +217,12 @@ __device__ __forceinline__ void wait_flag_acquire(int* flag) {
   while (__hip_atomic_load(flag, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) == 0) __builtin_amdgcn_s_sleep(1);
   asm volatile("buffer_inv sc0" ::: "memory");
 }
+template <bool ROOT_ROW = false>  // the rows entries: roots is indexed by root_row, not by tree
 __device__ __forceinline__ int select_descend(const DevPreset& dp, const DevMcts& m, int t,
                                               const uint32_t* __restrict__ roots, const int32_t* __restrict__ active,
                                               double cpuct, int32_t* __restrict__ status_out, uint32_t* lds,
                                               uint64_t pend_key = 0, int* const* pend = nullptr,
-                                              double root_eps = 1e-6) {
+                                              double root_eps = 1e-6, int root_row = -1) {
   uint32_t* s = lds;
   uint64_t* fa = reinterpret_cast<uint64_t*>(lds + kStateWords);
   const int l = lane_id();
@@ -234,7 +235,7 @@ __device__ __forceinline__ int select_descend(const DevPreset& dp, const DevMcts
     return 0;
   }
   BK_STAMP(0, 0);
-  load_state(s, roots + (size_t)t * kStateWords);
+  load_state(s, roots + (size_t)(ROOT_ROW ? root_row : t) * kStateWords);
   BK_BOARD_SYNC();
   BK_STAMP(0, 1);
   double cp = cpuct, eps = root_eps;
@@ -647,6 +648,7 @@ __device__ __forceinline__ void leaf_logits_tree(const DevPreset& dp, const DevM
 // dependent round trips as the data allows: (1) status, depth, node/child counters, leaf key and
 // K together; (2) the probe, the logit gather and the path records together; (3) the path
 // children's N and Q; then the stores.
+template <bool ZV = false>  // ZV (the rows entries): null values are an uninformed seat's zeros
 __device__ __forceinline__ void expand_tree(const DevPreset& dp, const DevMcts& m, int t, const float* __restrict__ logp,
                                             const float* __restrict__ values, int prior_mode, uint32_t* lds) {
   uint32_t* m32 = lds;  // W32pad words
@@ -770,7 +772,7 @@ __device__ __forceinline__ void expand_tree(const DevPreset& dp, const DevMcts& 
     } else if (l == 0) {
       atomicOr(&m.counters[kCtrErr], (unsigned long long)err);
     }
-    if (l < dp.P) vsh[l] = (double)values[(size_t)t * dp.P + l];
+    if (l < dp.P) vsh[l] = ZV && !values ? 0.0 : (double)values[(size_t)t * dp.P + l];
   } else {
     if (l < dp.P) vsh[l] = m.leaf_scores[(size_t)t * kMaxP + l];
   }
@@ -829,6 +831,7 @@ struct StepHead {
 };
 // status: the tree's leaf status as the step found it (read once, before any wave of the step can
 // run the next descent, which rewrites leaf_status)
+template <bool ZV = false>  // as expand_tree
 __device__ __forceinline__ StepHead backup_first(const DevMcts& m, int t, int P, const float* __restrict__ values,
                                                  int status) {
   __shared__ double vsh[kMaxP];
@@ -845,7 +848,7 @@ __device__ __forceinline__ StepHead backup_first(const DevMcts& m, int t, int P,
   const int64_t pchild = on_path ? m.path_child[pi] : 0;
   const int ppl = on_path ? m.path_pl[pi] : 0;
   if (h.status == 1) {
-    if (l < P) vsh[l] = (double)values[(size_t)t * P + l];
+    if (l < P) vsh[l] = ZV && !values ? 0.0 : (double)values[(size_t)t * P + l];
   } else {
     if (l < P) vsh[l] = m.leaf_scores[(size_t)t * kMaxP + l];
   }

@@ -254,6 +254,52 @@ __global__ __launch_bounds__(kFinThreads) void k_ply_finish(int G, int P, const 
   }
 }
 
+// The arena ply's tail (BatchedArena.play's bookkeeping after next_state / game_ended), one
+// workgroup: scores latched for the games that ended this ply, over, the illegal-move flag, and
+// the three row tables of the next ply from the next states' to_move.
+__global__ __launch_bounds__(kFinThreads) void k_arena_finish(int R, int P, const uint32_t* __restrict__ next_states,
+                                                              const int32_t* __restrict__ ended,
+                                                              const double* __restrict__ scores,
+                                                              const int32_t* __restrict__ status,
+                                                              const int32_t* __restrict__ orders,
+                                                              const int32_t* __restrict__ seat_net,
+                                                              const int32_t* __restrict__ seat_sims,
+                                                              int32_t* __restrict__ tree_of_row,
+                                                              int32_t* __restrict__ net_of_row,
+                                                              int32_t* __restrict__ sims_of_row,
+                                                              uint8_t* __restrict__ over, double* __restrict__ final,
+                                                              int32_t* __restrict__ illegal,
+                                                              int32_t* __restrict__ running) {
+  __shared__ int run_sh, bad_sh;
+  if (threadIdx.x == 0) {
+    run_sh = 0;
+    bad_sh = 0;
+  }
+  __syncthreads();
+  for (int r = threadIdx.x; r < R; r += kFinThreads) {
+    const bool was_over = over[r] != 0;
+    const bool end = ended[r] != 0;
+    if (!was_over && status[r] != 0) atomicOr(&bad_sh, 1);
+    if (end && !was_over)
+      for (int q = 0; q < P; ++q) final[(size_t)r * P + q] = scores[(size_t)r * P + q];
+    const bool now_over = was_over || end;
+    over[r] = now_over ? 1 : 0;
+    int tm = (int)next_states[(size_t)r * kStateWords + kWToMove];
+    tm = tm < 0 ? 0 : (tm >= P ? P - 1 : tm);  // a state's to_move is always a player
+    int pl = orders[(size_t)r * P + tm];
+    pl = pl < 0 ? 0 : (pl >= P ? P - 1 : pl);
+    tree_of_row[r] = now_over ? -1 : r * P + pl;
+    net_of_row[r] = seat_net[pl];
+    sims_of_row[r] = seat_sims[pl];
+    if (!now_over) atomicAdd(&run_sh, 1);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    *running = run_sh;
+    if (bad_sh) *illegal = 1;
+  }
+}
+
 }  // namespace
 }  // namespace bk
 
@@ -295,6 +341,21 @@ int bk_ply_finish(int G, int P, const int32_t* ended, const double* scores, cons
                      active, first_ply, reset_flags, game_id_out, (uint32_t*)roots_out, z_table, z_known, zcap,
                      next_gid, fin_count, sims_count, cap_overflow);
   return launch_check("k_ply_finish");
+}
+
+int bk_arena_finish(int R, int P, const void* next_states, const int32_t* ended, const double* scores,
+                    const int32_t* status, const int32_t* orders, const int32_t* seat_net, const int32_t* seat_sims,
+                    int32_t* tree_of_row, int32_t* net_of_row, int32_t* sims_of_row, uint8_t* over, double* final,
+                    int32_t* illegal, int32_t* running, void* stream) {
+  BK_REQUIRE(next_states && ended && scores && status && orders && seat_net && seat_sims && tree_of_row &&
+                 net_of_row && sims_of_row && over && final && illegal && running,
+             "bk_arena_finish: bad argument");
+  BK_REQUIRE(R >= 0 && P > 0 && P <= kMaxP, "bk_arena_finish: bad sizes");
+  BK_REQUIRE(((uintptr_t)next_states & 3u) == 0, "bk_arena_finish: states must be 4-byte aligned");
+  hipLaunchKernelGGL(k_arena_finish, dim3(1), dim3(kFinThreads), 0, (hipStream_t)stream, R, P,
+                     (const uint32_t*)next_states, ended, scores, status, orders, seat_net, seat_sims, tree_of_row,
+                     net_of_row, sims_of_row, over, final, illegal, running);
+  return launch_check("k_arena_finish");
 }
 
 }  // extern "C"

@@ -59,6 +59,12 @@ _SIGS = {
     "bk_mcts_counters": (_i, [_vp, _vp, _vp]),
     "bk_mcts_leaf_info": (_i, [_vp, _vp, _vp, _vp]),
     "bk_mcts_leaf_states": (_i, [_vp, ctypes.POINTER(_vp)]),
+    "bk_mcts_select_rows": (_i, [_vp, _vp, _vp, ctypes.c_double, _vp, _vp]),
+    "bk_mcts_leaf_step_rows": (_i, [_vp, _vp, _i, _vp, ctypes.c_int64, _i, _vp, _vp, _i, _vp, ctypes.c_double, _vp,
+                                    _vp]),
+    "bk_arena_move": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "bk_arena_sims": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, ctypes.c_double, _vp, _vp]),
+    "bk_arena_finish": (_i, [_i, _i] + [_vp] * 15),
     "bk_ply_policy": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, ctypes.c_double, ctypes.c_double, ctypes.c_uint64,
                            ctypes.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "bk_ply_finish": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
@@ -123,6 +129,7 @@ _SIGS = {
                          + [_i, _vp, _vp, _vp, _i, _vp]),
     "bk_leafnet_x3_np_states": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp] + [_vp] * 8
                                 + [_vp, _vp, _vp, _i, _vp]),
+    "bk_leafnet_x3_rows": (_i, [_vp, _i, _vp, _i, _vp]),
     "bk_leafnet_w3_weight_bytes": (_i, []),
     "bk_leafnet_w3_supported": (_i, [_i]),
     "bk_leafnet_w3": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp] + [_vp] * 8 + [_i, _vp, _vp, _vp, _vp, _vp]),
@@ -137,6 +144,41 @@ class LeafnetArgs(ctypes.Structure):
                 + [(k, _vp) for k in ("wstem", "sstem", "bstem", "wtower", "stower", "btower", "bounds", "wp", "bp",
                                       "wv", "bv", "w1t", "b1", "w2", "b2", "pf", "vout")]
                 + [("np", _i)])
+
+
+ARENA_MAX_NETS = 4
+
+
+class ArenaRows(ctypes.Structure):
+    """bk_arena_rows (include/blokus_engine.h): the arena ply's three device int32[R] tables. The
+    struct holds raw addresses: keep the tensors alive while it is in use."""
+    _fields_ = [("tree_of_row", _vp), ("net_of_row", _vp), ("sims_of_row", _vp), ("R", _i), ("T", _i)]
+
+
+class ArenaHeads(ctypes.Structure):
+    """bk_arena_heads: the policy Linear (W [A, F], bias [A]) of each net of the arena's table."""
+    _fields_ = [("W", _vp * ARENA_MAX_NETS), ("bias", _vp * ARENA_MAX_NETS), ("n", _i)]
+
+
+def arena_rows(tree_of_row: torch.Tensor, net_of_row: torch.Tensor, sims_of_row: torch.Tensor, trees: int) -> ArenaRows:
+    """trees: the number of trees T (of the search, and rows of states / pf / vout)."""
+    R = tree_of_row.shape[0]
+    for t in (tree_of_row, net_of_row, sims_of_row):
+        assert t.dtype == torch.int32 and t.shape == (R,) and t.is_contiguous() and t.is_cuda
+    return ArenaRows(tree_of_row.data_ptr(), net_of_row.data_ptr(), sims_of_row.data_ptr(), R, int(trees))
+
+
+def arena_heads(heads) -> ArenaHeads:
+    """heads: [(weight [A, F] f32, bias [A] f32)] per net, at most ARENA_MAX_NETS."""
+    if len(heads) > ARENA_MAX_NETS:
+        raise EngineError(f"the arena's net table holds at most {ARENA_MAX_NETS} nets, got {len(heads)}")
+    h = ArenaHeads()
+    h.n = len(heads)
+    for k, (w, b) in enumerate(heads):
+        assert w.dtype == torch.float32 and b.dtype == torch.float32 and w.is_contiguous() and b.is_contiguous()
+        h.W[k] = w.data_ptr()
+        h.bias[k] = b.data_ptr()
+    return h
 
 
 class EngineError(RuntimeError):
@@ -276,6 +318,30 @@ class Engine:
         scores = torch.empty((B, self.P), dtype=torch.float64, device=self.device)
         _check(self.lib.bk_game_ended(self.h, _ptr(states), B, _ptr(ended), _ptr(scores), self._s()))
         return ended, scores
+
+    def next_state_into(self, states, actions, out, nxt, status):
+        """next_state into caller-owned buffers (no allocation: a per-ply loop can reuse them)."""
+        _check(self.lib.bk_next_state(self.h, _ptr(states), _ptr(actions), states.shape[0], _ptr(out), _ptr(nxt),
+                                      _ptr(status), self._s()))
+
+    def game_ended_into(self, states, ended, scores):
+        _check(self.lib.bk_game_ended(self.h, _ptr(states), states.shape[0], _ptr(ended), _ptr(scores), self._s()))
+
+    def arena_finish(self, next_states, ended, scores, status, orders, seat_net, seat_sims, tree_of_row, net_of_row,
+                     sims_of_row, over, final, illegal, running):
+        """The arena ply's tail in one launch (bk_arena_finish): final / over / illegal latched, the
+        three row tables rewritten in place for the next ply, running = the games not over."""
+        R, P = next_states.shape[0], self.P
+        assert orders.dtype == torch.int32 and orders.shape == (R, P)
+        assert seat_net.dtype == torch.int32 and seat_sims.dtype == torch.int32 and seat_net.shape == (P,)
+        assert over.dtype == torch.uint8 and final.dtype == torch.float64 and final.shape == (R, P)
+        assert scores.dtype == torch.float64 and illegal.dtype == torch.int32 and running.dtype == torch.int32
+        for t in (tree_of_row, net_of_row, sims_of_row, ended, status):
+            assert t.dtype == torch.int32 and t.shape == (R,)
+        _check(self.lib.bk_arena_finish(R, P, _ptr(next_states), _ptr(ended), _ptr(scores), _ptr(status),
+                                        _ptr(orders), _ptr(seat_net), _ptr(seat_sims), _ptr(tree_of_row),
+                                        _ptr(net_of_row), _ptr(sims_of_row), _ptr(over), _ptr(final), _ptr(illegal),
+                                        _ptr(running), self._s()))
 
     def observe(self, states: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
         B = states.shape[0]

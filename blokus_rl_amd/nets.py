@@ -514,6 +514,42 @@ def leafnet_x3_args(model: "LeafResNet", pf: torch.Tensor, v: torch.Tensor, obs:
     return a
 
 
+def leafnet_x3_table(models, pf: torch.Tensor, v: torch.Tensor, states, status: torch.Tensor):
+    """The net table of bk_leafnet_x3_rows / bk_arena_sims: one bk_leafnet_args per LeafResNet (at
+    most engine.ARENA_MAX_NETS), all reading states [T, 384] (a tensor or a device address) with
+    status [T] and writing pf [T, 2*N*N] / v [T, P]. The nets must agree in board size, players,
+    depth and kernel form; ValueError otherwise. The rows form runs one board per workgroup, so
+    the np form's boards_per_wg is pinned to 1. The caller keeps everything alive (see leafnet_x3_args)."""
+    from .engine import ARENA_MAX_NETS, LeafnetArgs
+
+    models = list(models)
+    if not 0 < len(models) <= ARENA_MAX_NETS:
+        raise ValueError(f"the net table holds 1 to {ARENA_MAX_NETS} nets, got {len(models)}")
+    for m in models:
+        if not (isinstance(m, LeafResNet) and m.takes_states()):
+            raise ValueError("the net table takes LeafResNets whose takes_states() holds")
+    shape = lambda m: (m.board_size, m.f.value_fc2.out_features, len(m.f.blocks), m.x3_entry(m.board_size))  # noqa: E731
+    if any(shape(m) != shape(models[0]) for m in models[1:]):
+        raise ValueError(f"the nets differ in (board, players, blocks, kernel form): {[shape(m) for m in models]}")
+    table = (LeafnetArgs * len(models))()
+    for k, m in enumerate(models):
+        a = leafnet_x3_args(m, pf, v, states=states, status=status)
+        if a.np:
+            a.np = 2  # boards_per_wg = 1
+        table[k] = a
+    return table
+
+
+def leafnet_x3_rows(table, rows, sim: int, device=None):
+    """bk_leafnet_x3_rows: the leaf net over the arena's rows (engine.arena_rows), each live row
+    with the weight set of its net; table from leafnet_x3_table (None or empty: nothing to run)."""
+    from .engine import _check, _stream, load_library
+
+    n = 0 if table is None else len(table)
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+    _check(load_library().bk_leafnet_x3_rows(table, n, ctypes.byref(rows), int(sim), _stream(dev)))
+
+
 _OBSERVERS: dict = {}
 
 
@@ -692,25 +728,30 @@ class LeafResNet(nn.Module):
                 self.register_buffer("u_tower", pack_tower([c.weight.detach() for c in convs]))
                 self.register_buffer("b_tower", torch.cat([c.bias.detach().float() for c in convs]).contiguous())
             self.x3 = (f.stem.in_channels == 8 or self.x3_boards == "all") and len(f.blocks) > 0
-            if self.x3:  # bk_leafnet_x3's operands: split f16 weights + inverse scales
-                ws, ss, bs = pack_x3_stem(f.stem.weight, f.stem.bias)
-                self.register_buffer("x3_wstem", ws)
-                self.register_buffer("x3_sstem", ss)
-                packs = [pack_x3(c.weight, c.bias) for c in convs]
-                self.register_buffer("x3_wtower", torch.cat([p[0] for p in packs]).contiguous())
-                self.register_buffer("x3_stower", torch.cat([p[1] for p in packs]).contiguous())
-                self.register_buffer("x3_bounds", torch.cat([bs] + [p[2] for p in packs]).contiguous())
-                # bk_leafnet_w3's tower operands: split Winograd U + inverse scales
-                w3 = [pack_w3(c.weight) for c in convs]
-                self.register_buffer("w3_utower", torch.cat([p[0] for p in w3]).contiguous())
-                self.register_buffer("w3_stower", torch.cat([p[1] for p in w3]).contiguous())
-                c = lambda t: t.detach().float().contiguous().clone()  # noqa: E731
-                heads = [c(f.stem.bias), c(f.policy_conv.weight.view(2, 64)), c(f.policy_conv.bias),
-                         c(f.value_conv.weight.view(64)), c(f.value_conv.bias), c(f.value_fc1_wt()),
-                         c(f.value_fc1.bias), c(f.value_fc2.weight), c(f.value_fc2.bias)]
-                # registered buffers, so .to(device) / state_dict see them like the weight packs
-                for i, t in enumerate(heads):
-                    self.register_buffer(f"x3_head{i}", t)
+            if self.x3:
+                self._register_x3(convs)
+
+    def _register_x3(self, convs):
+        """bk_leafnet_x3's operands as buffers: split f16 weights + inverse scales, the heads."""
+        f = self.f
+        ws, ss, bs = pack_x3_stem(f.stem.weight, f.stem.bias)
+        self.register_buffer("x3_wstem", ws)
+        self.register_buffer("x3_sstem", ss)
+        packs = [pack_x3(c.weight, c.bias) for c in convs]
+        self.register_buffer("x3_wtower", torch.cat([p[0] for p in packs]).contiguous())
+        self.register_buffer("x3_stower", torch.cat([p[1] for p in packs]).contiguous())
+        self.register_buffer("x3_bounds", torch.cat([bs] + [p[2] for p in packs]).contiguous())
+        # bk_leafnet_w3's tower operands: split Winograd U + inverse scales
+        w3 = [pack_w3(c.weight) for c in convs]
+        self.register_buffer("w3_utower", torch.cat([p[0] for p in w3]).contiguous())
+        self.register_buffer("w3_stower", torch.cat([p[1] for p in w3]).contiguous())
+        c = lambda t: t.detach().float().contiguous().clone()  # noqa: E731
+        heads = [c(f.stem.bias), c(f.policy_conv.weight.view(2, 64)), c(f.policy_conv.bias),
+                 c(f.value_conv.weight.view(64)), c(f.value_conv.bias), c(f.value_fc1_wt()),
+                 c(f.value_fc1.bias), c(f.value_fc2.weight), c(f.value_fc2.bias)]
+        # registered buffers, so .to(device) / state_dict see them like the weight packs
+        for i, t in enumerate(heads):
+            self.register_buffer(f"x3_head{i}", t)
 
     @property
     def x3_heads(self) -> list[torch.Tensor]:

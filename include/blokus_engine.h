@@ -599,6 +599,79 @@ int bk_mcts_sims_pipelined(bk_mcts* m, const bk_leafnet_args* net, int n_sims, i
                            const float* bias, const void* roots, const int32_t* active, double cpuct,
                            int32_t* leaf_status, float* obs, void* stream);
 
+/* ---------------------------------------------------------------- batched arena (rows)
+ * The arena (arena.py:10-87, players/mcts_player.py:8-28) plays R games at once with one tree per
+ * (game, player): T = R x P trees, of which each game's ply uses one, the tree of the seat to
+ * move. A ply is described by three device tables of R rows (one row = one game):
+ *   tree_of_row[r]  the absolute tree g*P + player, or -1 when the game is over (the row does
+ *                   nothing anywhere);
+ *   net_of_row[r]   an index into a table of at most BK_ARENA_MAX_NETS nets, or -1 for an
+ *                   uninformed seat (DumbNet: every logit 0, value 0);
+ *   sims_of_row[r]  this ply's simulation budget of the seat to move.
+ * Row r is live at simulation s iff tree_of_row[r] >= 0 && s < sims_of_row[r]. Every entry below
+ * runs one workgroup per row; a row that is not live exits before touching anything. Whatever
+ * the search keeps per tree (leaf_status, the leaf-state buffer, pf, vout) stays indexed by
+ * absolute tree, as in the *_range entries; roots is indexed by row, [R][384 bytes]. */
+#define BK_ARENA_MAX_NETS 4
+typedef struct bk_arena_rows {
+  const int32_t* tree_of_row;
+  const int32_t* net_of_row;
+  const int32_t* sims_of_row;
+  int R;
+  int T; /* the number of trees: a row whose tree_of_row is >= T does nothing either */
+} bk_arena_rows;
+/* The policy Linear (W [A][F], bias [A]) of each net of the table (bk_mcts_leaf_step's W, bias). */
+typedef struct bk_arena_heads {
+  const float* W[BK_ARENA_MAX_NETS];
+  const float* bias[BK_ARENA_MAX_NETS];
+  int n;
+} bk_arena_heads;
+
+/* bk_leafnet_x3_states / bk_leafnet_x3_np_states (one board per workgroup) over rows, each with
+ * its own weight set: nets[k], k < nnets <= BK_ARENA_MAX_NETS, share states, status, pf, vout, N,
+ * P, nlayers and np (else BK_EINVAL; obs must be NULL: states form only) and differ in the weight
+ * and head pointers. Row r is evaluated iff it is live at `sim`, net_of_row[r] >= 0 and
+ * status[tree] == 1: it reads state row `tree` and writes pf / vout row `tree` with weight set
+ * net_of_row[r], bitwise what the states entry gives for that state and net. Every other row's
+ * outputs are NOT written (unlike the states entries, which evaluate dead rows as the all-zero
+ * observation). nnets = 0 launches nothing. */
+int bk_leafnet_x3_rows(const bk_leafnet_args* nets, int nnets, const bk_arena_rows* rows, int sim, void* stream);
+
+/* The descent of simulation 0 for every row live at 0 (bk_mcts_select on tree_of_row[r] from
+ * roots[r]): writes the leaf's state, bitmask and status; no observation planes, no mask copy. */
+int bk_mcts_select_rows(bk_mcts* m, const bk_arena_rows* rows, const void* roots, double cpuct,
+                        int32_t* leaf_status, void* stream);
+/* bk_mcts_leaf_step for every row live at `sim`, with the policy Linear heads->W / bias
+ * [net_of_row[r]]; net_of_row[r] == -1: every logit is 0 and the value is 0 (the expansion's
+ * softmax subtracts the maximum, so the priors are bitwise those of any constant log-prior row).
+ * When do_select && sim + 1 < sims_of_row[r] the next descent runs too. feat [T][ldf], values
+ * [T][P] by absolute tree. BK_STEP_OVERLAP selects the kernel as in bk_mcts_leaf_step. */
+int bk_mcts_leaf_step_rows(bk_mcts* m, const bk_arena_rows* rows, int sim, const float* feat, int64_t ldf, int F,
+                           const bk_arena_heads* heads, const float* values, int do_select, const void* roots,
+                           double cpuct, int32_t* leaf_status, void* stream);
+/* The arena's move (get_distribution at temperature 0 + np.argmax, mcts_player.py:27-28) straight
+ * from the tree: action[r] = the id of the first child with maximal N of the root roots[r] of
+ * tree_of_row[r]; -1 when the row is dead or the root has no child; a root that is not in the
+ * tree sets error bit 4 (action -1). */
+int bk_arena_move(bk_mcts* m, const bk_arena_rows* rows, const void* roots, int32_t* action, void* stream);
+/* A whole ply's search on one stream, no forked branches (under capture: a linear graph):
+ * bk_mcts_select_rows, then for s < max_sims { bk_leafnet_x3_rows(s), bk_mcts_leaf_step_rows(s,
+ * do_select = s + 1 < max_sims) } with feat = nets[0].pf, values = nets[0].vout, F = 2 N^2.
+ * nnets = 0 (uninformed seats only): pf and vout must still be given through `pf` / `vout`. */
+int bk_arena_sims(bk_mcts* m, const bk_leafnet_args* nets, int nnets, const bk_arena_rows* rows, int max_sims,
+                  const bk_arena_heads* heads, const float* pf, const float* vout, const void* roots, double cpuct,
+                  int32_t* leaf_status, void* stream);
+/* The arena ply's tail after bk_next_state / bk_game_ended on the R games (one launch, one
+ * workgroup): for a game not yet over, final[r][P] = scores[r] when ended[r] (arena.py:73-77),
+ * over[r] |= ended[r], *illegal = 1 if status[r] != 0 (bk_next_state's); the three row tables are
+ * rewritten in place for the next ply from next_states' to_move: player = orders[r][to_move],
+ * tree = r*P + player (-1 when over), net = seat_net[player], sims = seat_sims[player];
+ * *running = the games not over. */
+int bk_arena_finish(int R, int P, const void* next_states, const int32_t* ended, const double* scores,
+                    const int32_t* status, const int32_t* orders, const int32_t* seat_net, const int32_t* seat_sims,
+                    int32_t* tree_of_row, int32_t* net_of_row, int32_t* sims_of_row, uint8_t* over, double* final,
+                    int32_t* illegal, int32_t* running, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
