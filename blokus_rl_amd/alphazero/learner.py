@@ -133,10 +133,12 @@ class Learner:
 
     def __init__(self, model: torch.nn.Module, lr: float = 1e-3, weight_decay: float = 1e-4, batch_size: int = 64,
                  seed: int = 0, policy_fn=policy_loss, group=None, optimizer: torch.optim.Optimizer | None = None,
-                 device_path: bool | str = "auto"):
+                 device_path: bool | str = "auto", x3_boards: str | None = None):
         """device_path: train the ResNet on train_conv's device path (tower convs on bk_conv_x3,
         channels_last, PyTorch batch norm; switched in place) — True, False, or "auto" = on a GPU
-        at batch_size >= 256 (the large batches where the fp32 convolutions dominate a step)."""
+        at batch_size >= 256 (the large batches where the fp32 convolutions dominate a step).
+        x3_boards ("classic" | "all" | None = BK_X3_BOARDS): under "all" a 7x7 or 14x14 ResNet's
+        tower convs run on bk_conv_x3_np too; under "classic" they stay on PyTorch's fp32 ones."""
         self.model = model
         self.batch_size = batch_size
         on_gpu = next(model.parameters()).is_cuda
@@ -145,9 +147,14 @@ class Learner:
         self.device_path = bool(device_path)
         if self.device_path:
             from .train_conv import TrainResNet, prepare_model
-            prepare_model(model)
-            # the policy Linear at the batch's legal ids only (trainfc.hip), with the reference loss
-            self.sparse_head = isinstance(model, TrainResNet) and policy_fn is policy_loss
+            prepare_model(model, x3_boards=x3_boards)
+            # the policy Linear at the batch's legal ids only (trainfc.hip), with the reference loss:
+            # where the training forward really is the fused one (TrainResNet on a board its mode
+            # covers) and bk_sparse_linear_* takes the head (feature rows of whole float4s, at most
+            # 1024 features, at most 4096 rows); otherwise the dense head
+            self.sparse_head = (isinstance(model, TrainResNet) and model.fused_for_board(model.board_x)
+                                and policy_fn is policy_loss and model.policy_out.in_features % 4 == 0
+                                and model.policy_out.in_features <= 1024 and batch_size <= 4096)
         else:
             self.sparse_head = False
         self.policy_fn = policy_fn
@@ -170,7 +177,7 @@ class Learner:
         obs = batch["observation"]
         if self.device_path:
             obs = obs.contiguous(memory_format=torch.channels_last)
-        if self.sparse_head:
+        if self.sparse_head and obs.shape[0] <= 4096:
             xs, v_pred = self.net(obs, ids=batch["ids"], k=batch["k"])
             loss = sparse_policy_loss(xs, batch["pi"], batch["k"]) + (v_pred.squeeze() - batch["score"]).pow(2).mean()
         else:

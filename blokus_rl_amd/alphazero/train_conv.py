@@ -8,6 +8,10 @@ the fp32 convolutions (MIOpen igemm / Winograd on the f32 MFMA, 1/16 of the f16 
 take most of a large-batch step. `ConvX3Function` runs a conv's forward and its input gradient
 through bk_conv_x3 and its weight gradient through bk_conv_x3_wgrad; `prepare_model` switches a
 ResNet to that path in place without touching its parameters or state_dict keys.
+
+Boards: 20x20 always (bk_conv_x3); 7x7 and 14x14 on bk_conv_x3_np / bk_conv_x3_np_wgrad when the
+model was prepared with x3_boards="all" (BK_X3_BOARDS, nets.x3_boards_mode; the default "classic"
+leaves those boards on PyTorch's fp32 convolutions). `train_entry` is the one eligibility rule.
 """
 from __future__ import annotations
 
@@ -19,7 +23,7 @@ from torch import nn
 from ..engine import _check, _ptr, _stream, load_library
 import torch.nn.functional as F
 
-from ..nets import NativeBatchNorm2d, ResNet, use_native_batchnorm
+from ..nets import NativeBatchNorm2d, ResNet, use_native_batchnorm, x3_boards_mode
 
 
 def pack_weight(weight: torch.Tensor, flip: bool) -> tuple[torch.Tensor, torch.Tensor]:
@@ -69,15 +73,76 @@ def conv_x3_wgrad(x: torch.Tensor, gy: torch.Tensor) -> torch.Tensor:
     return dw
 
 
+def train_entry(N: int, channels: int, mode: str) -> str | None:
+    """Which kernels train a 3x3 conv of `channels` -> `channels` on NxN boards under the board mode
+    `mode` ("classic" or "all"): "x3" (bk_conv_x3: 20x20), "np" (bk_conv_x3_np: 7x7 and 14x14, under
+    "all" only) or None (PyTorch's fp32 convolution)."""
+    if mode not in ("classic", "all"):
+        raise ValueError(f"x3_boards must be classic or all, got {mode!r}")
+    if channels != 64:
+        return None
+    if N == 20:
+        return "x3"
+    if mode == "all" and N in (7, 14) and load_library().bk_conv_x3_np_supported(int(N)):
+        return "np"
+    return None
+
+
+def conv_x3_np(x: torch.Tensor, ws: torch.Tensor, inv: torch.Tensor, bias: torch.Tensor | None) -> torch.Tensor:
+    """bk_conv_x3_np on a channels_last [B, 64, N, N] f32 activation, N in (7, 14) -> the same shape,
+    channels_last; ws / inv from pack_weight. A board's output does not depend on the batch."""
+    lib = load_library()
+    if x.dim() != 4 or x.shape[1] != 64 or x.shape[2] != x.shape[3] or x.shape[2] not in (7, 14) \
+            or x.dtype != torch.float32 or not x.is_cuda:
+        raise ValueError(f"conv_x3_np takes a [B, 64, N, N] f32 device tensor with N in (7, 14), got "
+                         f"{tuple(x.shape)} {x.dtype}")
+    B, N = x.shape[0], x.shape[2]
+    x = x.contiguous(memory_format=torch.channels_last)
+    y = torch.empty((B, 64, N, N), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+    b = None
+    if bias is not None:
+        b = bias.detach()
+        b = b if (b.dtype == torch.float32 and b.is_contiguous()) else b.float().contiguous()
+    _check(lib.bk_conv_x3_np(ctypes.c_void_p(x.data_ptr()), B, N, _ptr(ws), _ptr(inv), _ptr(b) if b is not None else None,
+                             ctypes.c_void_p(y.data_ptr()), _stream(x.device)))
+    return y
+
+
+def conv_x3_np_wgrad(x: torch.Tensor, gy: torch.Tensor) -> torch.Tensor:
+    """bk_conv_x3_np_wgrad: the weight gradient [64, 64, 3, 3] of the 64->64 conv on 7x7 or 14x14
+    boards from its input x and output gradient gy (channels_last [B, 64, N, N] f32); deterministic."""
+    lib = load_library()
+    if x.dim() != 4 or tuple(x.shape[1:]) not in ((64, 7, 7), (64, 14, 14)) or x.shape != gy.shape \
+            or x.dtype != torch.float32 or gy.dtype != torch.float32 or not x.is_cuda:
+        raise ValueError("conv_x3_np_wgrad takes two [B, 64, N, N] f32 device tensors with N in (7, 14)")
+    B, N = x.shape[0], x.shape[2]
+    x = x.contiguous(memory_format=torch.channels_last)
+    gy = gy.contiguous(memory_format=torch.channels_last)
+    ws = torch.empty(lib.bk_conv_x3_np_wgrad_workspace_floats(B, N), dtype=torch.float32, device=x.device)
+    dw = torch.empty((64, 64, 3, 3), dtype=torch.float32, device=x.device)
+    _check(lib.bk_conv_x3_np_wgrad(ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(gy.data_ptr()), B, N, _ptr(ws),
+                                   _ptr(dw), _stream(x.device)))
+    return dw
+
+
+def _conv(x, ws, inv, bias):
+    """The split-f16 conv of the activation's board size (20x20: bk_conv_x3, else bk_conv_x3_np)."""
+    return conv_x3(x, ws, inv, bias) if x.shape[2] == 20 else conv_x3_np(x, ws, inv, bias)
+
+
+def _wgrad(x, gy):
+    return conv_x3_wgrad(x, gy) if x.shape[2] == 20 else conv_x3_np_wgrad(x, gy)
+
+
 class ConvX3Function(torch.autograd.Function):
     """y = conv2d(x, weight, bias, padding=1) with the forward, the input gradient and the weight
-    gradient on bk_conv_x3 / bk_conv_x3_wgrad; the bias gradient the sum of dy over batch and
+    gradient on bk_conv_x3 / bk_conv_x3_wgrad (7x7, 14x14: their _np forms); the bias gradient the sum of dy over batch and
     pixels."""
 
     @staticmethod
     def forward(ctx, x, weight, bias):
         ws, inv = pack_weight(weight, flip=False)
-        y = conv_x3(x, ws, inv, bias)
+        y = _conv(x, ws, inv, bias)
         ctx.save_for_backward(x, weight)
         ctx.has_bias = bias is not None
         return y
@@ -90,9 +155,9 @@ class ConvX3Function(torch.autograd.Function):
         gx = gw = gb = None
         if ctx.needs_input_grad[0]:
             ws, inv = pack_weight(weight, flip=True)
-            gx = conv_x3(gy, ws, inv, None)
+            gx = _conv(gy, ws, inv, None)
         if ctx.needs_input_grad[1]:
-            gw = conv_x3_wgrad(x, gy)
+            gw = _wgrad(x, gy)
         if ctx.has_bias and ctx.needs_input_grad[2]:
             gb = gy.sum(dim=(0, 2, 3))
         return gx, gw, gb
@@ -164,7 +229,7 @@ class ConvBNFunction(torch.autograd.Function):
     def forward(ctx, x, cw, cb, gamma, beta, running_mean, running_var, momentum, eps, relu):
         ws, inv = pack_weight(cw, flip=False)
         x = x.contiguous(memory_format=torch.channels_last)
-        z = conv_x3(x, ws, inv, cb)
+        z = _conv(x, ws, inv, cb)
         y, stats = bn_forward(z, gamma, beta, running_mean, running_var, momentum, eps, relu)
         ctx.save_for_backward(x, cw, z, gamma, stats)
         ctx.relu, ctx.has_bias = bool(relu), cb is not None
@@ -180,9 +245,9 @@ class ConvBNFunction(torch.autograd.Function):
         gx = gw = None
         if ctx.needs_input_grad[0]:
             ws, inv = pack_weight(cw, flip=True)
-            gx = conv_x3(dz, ws, inv, None)
+            gx = _conv(dz, ws, inv, None)
         if ctx.needs_input_grad[1]:
-            gw = conv_x3_wgrad(x, dz)
+            gw = _wgrad(x, dz)
         return gx, gw, dcb, dg, db, None, None, None, None, None
 
 
@@ -219,23 +284,28 @@ def _eligible(m: nn.Module) -> bool:
 
 class X3Conv2d(nn.Conv2d):
     """nn.Conv2d (same parameters and state_dict keys) whose 20x20 64->64 device calls in training
-    (train mode, gradients enabled) run ConvX3Function; anything else (eval mode, no_grad /
-    inference, CPU, other shapes) takes nn.Conv2d's own fp32 path."""
+    (train mode, gradients enabled) run ConvX3Function, and with x3_boards == "all" its 7x7 and
+    14x14 ones too (train_entry); anything else (eval mode, no_grad / inference, CPU, other shapes)
+    takes nn.Conv2d's own fp32 path."""
+
+    x3_boards = "classic"  # the board mode the module was prepared with (use_x3_convs)
 
     def forward(self, x):
-        if (self.training and torch.is_grad_enabled() and x.is_cuda and x.dim() == 4
-                and tuple(x.shape[1:]) == (64, 20, 20) and x.dtype == torch.float32):
+        if (self.training and torch.is_grad_enabled() and x.is_cuda and x.dim() == 4 and x.dtype == torch.float32
+                and x.shape[2] == x.shape[3] and train_entry(x.shape[2], x.shape[1], self.x3_boards) is not None):
             return ConvX3Function.apply(x, self.weight, self.bias)
         return super().forward(x)
 
 
-def use_x3_convs(model: nn.Module) -> int:
-    """Switch every eligible Conv2d (3x3, 64 -> 64, stride 1, padding 1) to X3Conv2d in place;
-    returns how many were switched."""
+def use_x3_convs(model: nn.Module, x3_boards: str | None = None) -> int:
+    """Switch every eligible Conv2d (3x3, 64 -> 64, stride 1, padding 1) to X3Conv2d in place, with
+    the board mode x3_boards (None: BK_X3_BOARDS) stored on each; returns how many were switched."""
+    mode = x3_boards_mode(x3_boards)
     k = 0
     for m in model.modules():
         if _eligible(m):
             m.__class__ = X3Conv2d
+            m.x3_boards = mode
             k += 1
     return k
 
@@ -305,7 +375,8 @@ def _conv_bn(conv: nn.Module, bn: nn.Module, x: torch.Tensor, relu: bool) -> tor
 
 class TrainResNet(ResNet):
     """nets.ResNet (same modules, parameters and state_dict keys) whose training forward (train
-    mode, gradients enabled, 20x20 f32 on the device) runs each residual block's conv -> BN -> ReLU
+    mode, gradients enabled, f32 on the device, a board train_entry accepts under the model's
+    x3_boards mode: 20x20, or 7x7 / 14x14 under "all") runs each residual block's conv -> BN -> ReLU
     and conv -> BN as one ConvBNFunction each and the stem's BN -> ReLU as one BatchNormFunction,
     and returns the policy head's raw logits instead of their log-softmax: the learner's loss is
     the masked log-softmax over the legal ids (bk_policy_loss, neural_network.py:138-157), which is
@@ -313,11 +384,18 @@ class TrainResNet(ResNet):
     so the dense log-softmax (a [B, A] pass each way) changes neither the loss nor the gradients.
     Every other forward (eval, no_grad, CPU) is ResNet's own."""
 
+    x3_boards = "classic"  # the board mode the model was prepared with (prepare_model)
+
+    def fused_for_board(self, N: int) -> bool:
+        """Whether a training forward on NxN boards is the fused one (the call's own conditions —
+        train mode, gradients, f32 on the device — aside): the learner's head choice reads this."""
+        return (train_entry(N, 64, self.x3_boards) is not None and _bn_ok(self.bn1)
+                and all(len(b) == 5 and _eligible_x3(b[0]) and _eligible_x3(b[3]) and _bn_ok(b[1]) and _bn_ok(b[4])
+                        and isinstance(b[2], nn.ReLU) for b in self.res_blocks))
+
     def _fused_ok(self, x: torch.Tensor) -> bool:
         return (self.training and torch.is_grad_enabled() and x.is_cuda and x.dtype == torch.float32
-                and x.dim() == 4 and x.shape[2] == 20 and x.shape[3] == 20 and _bn_ok(self.bn1)
-                and all(_eligible_x3(b[0]) and _eligible_x3(b[3]) and _bn_ok(b[1]) and _bn_ok(b[4])
-                        and isinstance(b[2], nn.ReLU) and len(b) == 5 for b in self.res_blocks))
+                and x.dim() == 4 and x.shape[2] == x.shape[3] and self.fused_for_board(x.shape[2]))
 
     def forward(self, x, ids: torch.Tensor | None = None, k: torch.Tensor | None = None):
         """ids / k (the batch's legal ids [B, cap] int16 and counts [B] int32): the policy head
@@ -349,17 +427,31 @@ def _eligible_x3(m: nn.Module) -> bool:
         and m.padding_mode == "zeros"
 
 
-def prepare_model(model: nn.Module, x3_convs: bool = True, fused_bn: bool = True) -> nn.Module:
+def prepare_model(model: nn.Module, x3_convs: bool = True, fused_bn: bool = True,
+                  x3_boards: str | None = None) -> nn.Module:
     """The device training path IN PLACE on the caller's model (Learner(device_path="auto") calls
     it): channels_last parameters, PyTorch batch norm (the 64-channel ones on bk_bn_forward /
     bk_bn_backward when fused_bn), and (x3_convs) the tower convs on bk_conv_x3. The swapped
     classes keep the parameters and state_dict keys; their eval-mode and no-grad forwards are
-    PyTorch's fp32 ones, so a deepcopy of the model (e.g. the trainer's pnet) evaluates in fp32."""
+    PyTorch's fp32 ones, so a deepcopy of the model (e.g. the trainer's pnet) evaluates in fp32.
+    x3_boards ("classic" | "all" | None = BK_X3_BOARDS): under "all" the 7x7 and 14x14 tower convs
+    run on bk_conv_x3_np as well; the resolved mode is stored on the swapped modules, so a model
+    prepared once keeps it (a later call with x3_boards=None changes nothing)."""
     use_native_batchnorm(model)
     if fused_bn:
         use_fused_batchnorm(model)
+    if x3_boards is None and isinstance(model, TrainResNet):
+        mode = model.x3_boards
+    else:
+        mode = x3_boards_mode(x3_boards)
     if x3_convs:
-        use_x3_convs(model)
+        use_x3_convs(model, mode)
+        if x3_boards is not None:
+            for m in model.modules():
+                if isinstance(m, X3Conv2d):
+                    m.x3_boards = mode
     if x3_convs and fused_bn and type(model) is ResNet:
         model.__class__ = TrainResNet  # the block-level fusion (conv + BN + ReLU per autograd node)
+    if isinstance(model, TrainResNet):
+        model.x3_boards = mode
     return model.to(memory_format=torch.channels_last)

@@ -83,6 +83,12 @@ _SIGS = {
     "bk_conv_x3": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "bk_conv_x3_wgrad_workspace_floats": (_i, [_i]),
     "bk_conv_x3_wgrad": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
+    "bk_conv_x3_np_supported": (_i, [_i]),
+    "bk_conv_x3_np_tile_boards": (_i, [_i]),
+    "bk_conv_x3_np": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "bk_conv_x3_np_wgrad_workspace_floats": (_i, [_i, _i]),
+    "bk_conv_x3_np_wgrad_tile_boards": (_i, [_i]),
+    "bk_conv_x3_np_wgrad": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
     "bk_bn_workspace_doubles": (_i, []),
     "bk_bn_forward": (_i, [_vp, ctypes.c_int64, _vp, _vp, _vp, _vp, ctypes.c_float, ctypes.c_float, _vp, _vp, _vp, _vp]),
     "bk_bn_backward": (_i, [_vp, _vp, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

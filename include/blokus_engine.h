@@ -324,6 +324,22 @@ int bk_conv_x3_wgrad(const float* x, const float* dy, int B, int N, float* works
 int bk_conv_x3_pack(const float* w, int flip, void* wsplit, float* inv, void* stream);
 int bk_conv_x3(const float* x, int B, int N, const void* wsplit, const float* inv, const float* bias, float* y,
                void* stream);
+/* The same convolution and weight gradient for 7x7 and 14x14 boards (trainconv_np.hip), on the
+ * operands of bk_conv_x3_pack: x, y, dy NHWC [B][N][N][64] f32, 16-byte aligned; bias may be NULL.
+ * Every board has its own power-of-two input scale, so a board's output is bitwise a function of
+ * that board and the weights alone (not of its tile neighbours, its place or the batch size).
+ * bk_conv_x3_np_supported(N): 1 for N = 7 and 14, else 0. bk_conv_x3_np_tile_boards(N): the boards
+ * that share one workgroup step (8 at 7x7, 1 at 14x14); bk_conv_x3_np_wgrad_tile_boards(N): the
+ * boards a workgroup of the weight gradient takes per trip (4 at 7x7, 1 at 14x14). workspace:
+ * bk_conv_x3_np_wgrad_workspace_floats(B, N) floats (partial sums, added in a fixed order:
+ * deterministic). B = 0 is valid: no launch, and the weight gradient is zeros. */
+int bk_conv_x3_np_supported(int N);
+int bk_conv_x3_np_tile_boards(int N);
+int bk_conv_x3_np(const float* x, int B, int N, const void* wsplit, const float* inv, const float* bias, float* y,
+                  void* stream);
+int bk_conv_x3_np_wgrad_workspace_floats(int B, int N);
+int bk_conv_x3_np_wgrad_tile_boards(int N);
+int bk_conv_x3_np_wgrad(const float* x, const float* dy, int B, int N, float* workspace, float* dw, void* stream);
 
 /* The learner's train-mode batch norm of a 64-channel NHWC activation x [M][64] f32 (M = batch
  * x pixels; nn.BatchNorm2d(64) of models/blokus_nnet.py:99-112 in neural_network.py:52-85's
