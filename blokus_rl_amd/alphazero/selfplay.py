@@ -50,7 +50,8 @@ class LeafEvaluator:
     v [G, P] f32). DumbNet needs no forward: a constant uniform log-prior and zero values."""
 
     def __init__(self, model: torch.nn.Module | None, eng: Engine, G: int, dtype: torch.dtype = torch.float32,
-                 use_graph: bool = True, sparse_policy: bool = True, x3_boards: str | None = None):
+                 use_graph: bool = True, sparse_policy: bool = True, x3_boards: str | None = None,
+                 dcnn_leaf: str | None = None):
         self.model = model
         self.eng = eng
         self.G = G
@@ -65,18 +66,21 @@ class LeafEvaluator:
             self.const_v = torch.zeros((G, eng.P), dtype=torch.float32, device=dev)
             self.model = None
             return
-        from ..nets import LeafResNet, inference_model
+        from ..nets import inference_model
         # raw policy logits are enough: k_expand_backup takes the softmax over the legal ids; with
-        # the HIP ResNet, even the policy Linear is left to the search (bk_mcts_leaf_logits computes
-        # only the leaf's legal ids' logits), so the net returns (policy features, v)
+        # a HIP leaf module (LeafResNet, or LeafDCNNet under dcnn_leaf / BK_DCNN_LEAF "x3"), even the
+        # policy Linear is left to the search (bk_mcts_leaf_logits computes only the leaf's legal
+        # ids' logits), so the net returns (policy features, v). The module declares both: its
+        # sparse_head() is that Linear (or None), planar_input whether it reads k_select's planes
         self.model = inference_model(model, normalize=False, dtype=dtype, features=sparse_policy,
-                                     x3_boards=x3_boards).to(
+                                     x3_boards=x3_boards, dcnn_leaf=dcnn_leaf).to(
             memory_format=torch.channels_last)
-        self.sparse = isinstance(self.model, LeafResNet) and self.model.native and sparse_policy
-        if isinstance(self.model, LeafResNet) and not self.sparse:
+        head = getattr(self.model, "sparse_head", None)
+        po = head() if head is not None else None
+        self.sparse = po is not None and sparse_policy
+        if head is not None and not self.sparse:
             self.model.features = False
         if self.sparse:
-            po = self.model.f.policy_out
             self.policy_w = po.weight.detach().float().contiguous()
             self.policy_b = po.bias.detach().float().contiguous()
             # the sparse head leaves out W float4s whose four features are zero (exact: 0 * w adds
@@ -87,9 +91,9 @@ class LeafEvaluator:
 
                 raise EngineError("the policy layer holds non-finite weights (diverged net): refusing the sparse "
                                   "policy head, whose zero-feature skip would hide the NaN logits")
-        # the HIP ResNet reads the planar observation k_select writes (the search can write straight
-        # into static_obs: no copy); the MIOpen paths want channels_last
-        self.planar = isinstance(self.model, LeafResNet) and self.model.native
+        # the HIP leaf modules read the planar observation k_select writes (the search can write
+        # straight into static_obs: no copy); the MIOpen paths want channels_last
+        self.planar = bool(getattr(self.model, "planar_input", False))
         self.static_obs = torch.zeros((G,) + eng.obs_shape, dtype=torch.float32, device=dev)
         if not self.planar:
             self.static_obs = self.static_obs.contiguous(memory_format=torch.channels_last)
@@ -161,7 +165,7 @@ class SelfPlay:
                  cap: int = 2048, seed: int = 0, nn_dtype: torch.dtype = torch.float32, use_graph: bool = True,
                  continuous: bool = False, sim_graph_sims: int | None = None, record_plies: int | None = None,
                  leaf_input: str | None = None, sim_groups: int | None = None, sim_ring: int | bool | None = None,
-                 sim_groups_min_games: int = 64, x3_boards: str | None = None):
+                 sim_groups_min_games: int = 64, x3_boards: str | None = None, dcnn_leaf: str | None = None):
         self.eng = eng
         self.G = games
         self.num_sims = num_sims
@@ -184,7 +188,10 @@ class SelfPlay:
         self.mcts = BatchedMCTS(eng, games, node_cap=node_cap, child_cap=child_cap)
         # x3_boards / BK_X3_BOARDS "all": the one-launch split-f16 leaf net (and with it leaf_input
         # "states" and the pipelined groups) also for 2- and 3-player nets and 7x7 boards
-        self.evaluator = LeafEvaluator(model, eng, games, nn_dtype, use_graph, x3_boards=x3_boards)
+        # dcnn_leaf / BK_DCNN_LEAF "x3": a DCNNet on the split-f16 convolutions with the sparse policy
+        # head (nets.LeafDCNNet; it takes no packed states: leaf_input "planes", one tree group)
+        self.evaluator = LeafEvaluator(model, eng, games, nn_dtype, use_graph, x3_boards=x3_boards,
+                                       dcnn_leaf=dcnn_leaf)
         self._use_graph = use_graph
         # what the leaf net reads: "planes" (the f32 observation the search writes per leaf) or
         # "states" (the search's packed leaf states and status: no observation is written inside the

@@ -112,6 +112,10 @@ _SIGS = {
     "bk_conv7_first_wgrad": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
     "bk_dropout_keep": (_i, [_vp, ctypes.c_int64, ctypes.c_float, _vp, _vp]),
     "bk_conv7_act_grad": (_i, [_vp, _vp, ctypes.c_int64, ctypes.c_float, _vp, _vp]),
+    "bk_conv128_x3_supported": (_i, [_i]),
+    "bk_conv128_x3_tile_boards": (_i, [_i]),
+    "bk_conv128_x3": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp]),
+    "bk_conv128_first": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp]),
     "bk_bias_act": (_i, [_vp, ctypes.c_int64, _i, _vp, _vp, _i, _vp]),
     "bk_conv3x3_packed_floats": (_i, [_i]),
     "bk_conv3x3_form": (_i, [_i, _i]),

@@ -6,7 +6,8 @@ semantics and `state_dict` keys follow the reference so its checkpoints load unc
   around the whole stack of `num_res_blocks` (conv-BN-ReLU-conv-BN) blocks, policy head
   1x1 conv(2)+BN+ReLU+Linear(2*N*N -> A)+log_softmax, value head 1x1 conv(1)+BN+ReLU+
   Linear(N*N -> 64)+ReLU+Linear(64 -> P)+tanh.
-* `DCNNet`  — blokus_nnet.py:9-85.
+* `DCNNet`  — blokus_nnet.py:9-85; as a leaf net optionally `LeafDCNNet` (dcnn_leaf / BK_DCNN_LEAF "x3":
+  the convolutions on csrc/conv128.hip, the sparse policy head).
 * `DumbNet` — models/dumbnet.py:6-21: logits 1, value 0 (the "uninformed MCTS" opponent).
 """
 from __future__ import annotations
@@ -781,6 +782,17 @@ class LeafResNet(nn.Module):
             return "np"
         return None
 
+    @property
+    def planar_input(self) -> bool:
+        """Whether forward reads the planar observation as the search writes it (the HIP kernels);
+        the MIOpen path wants channels_last."""
+        return self.native
+
+    def sparse_head(self):
+        """The Linear (policy_out) the search's sparse policy head applies to the policy features
+        (features=True), or None where the module has no HIP path."""
+        return self.f.policy_out if self.native else None
+
     def takes_states(self) -> bool:
         """Whether forward_states runs bk_leafnet_x3_states (else it observes and calls forward)."""
         return bool(self.x3 and net_math() == "x3" and self.x3_entry(self.board_size) is not None)
@@ -870,14 +882,248 @@ class LeafResNet(nn.Module):
         return (F.log_softmax(logits, dim=1) if self.normalize else logits), v
 
 
+def dcnn_leaf_mode(arg: str | None = None) -> str:
+    """How a DCNNet evaluates the leaf batch: "torch" (default) = model.eval() on PyTorch, "x3" =
+    LeafDCNNet (the convolutions on the split-f16 MFMA kernels, the sparse policy head). arg, else
+    BK_DCNN_LEAF."""
+    import os
+
+    m = arg if arg is not None else os.environ.get("BK_DCNN_LEAF", "torch")
+    if m not in ("torch", "x3"):
+        raise ValueError(f"dcnn_leaf / BK_DCNN_LEAF must be torch or x3, got {m!r}")
+    return m
+
+
+class FoldedDCNN:
+    """DCNNet's eval-mode function as plain tensors (fold_dcnn): conv_w / conv_b, the four
+    convolutions with their BatchNorm folded in ([128, cin, 3, 3], [128]); fc1_w with BatchNorm1d
+    folded in and its columns reordered from (c, r, col) to (r, col, c) — the NHWC order of the
+    cropped fourth activation; fc2_w / fc2_b likewise folded; fc3 (policy) and fc4 (value) as they
+    are. N = the board side."""
+
+    def __init__(self, N, conv_w, conv_b, fc1_w, fc1_b, fc2_w, fc2_b, fc3_w, fc3_b, fc4_w, fc4_b):
+        self.N = N
+        self.conv_w, self.conv_b = conv_w, conv_b
+        self.fc1_w, self.fc1_b, self.fc2_w, self.fc2_b = fc1_w, fc1_b, fc2_w, fc2_b
+        self.fc3_w, self.fc3_b, self.fc4_w, self.fc4_b = fc3_w, fc3_b, fc4_w, fc4_b
+
+
+@torch.no_grad()
+def fold_dcnn(model: DCNNet) -> FoldedDCNN:
+    """DCNNet -> FoldedDCNN in the model's dtype and on its device (eval-mode BatchNorm: the running
+    statistics)."""
+    def bn_scale(bn):
+        s = bn.weight / torch.sqrt(bn.running_var + bn.eps)
+        return s, bn.bias - bn.running_mean * s
+
+    conv_w, conv_b = [], []
+    for conv, bn in ((model.conv1, model.bn1), (model.conv2, model.bn2), (model.conv3, model.bn3),
+                     (model.conv4, model.bn4)):
+        s, t = bn_scale(bn)
+        conv_w.append((conv.weight * s.view(-1, 1, 1, 1)).contiguous())
+        conv_b.append((conv.bias * s + t).contiguous())
+    N, C, M = model.board_x, model.num_channels, model.board_x - 4
+    s, t = bn_scale(model.fc_bn1)
+    w1 = model.fc1.weight * s.view(-1, 1)
+    w1 = w1.view(-1, C, M, M).permute(0, 2, 3, 1).reshape(w1.shape[0], -1).contiguous()
+    b1 = (model.fc1.bias * s + t).contiguous()
+    s, t = bn_scale(model.fc_bn2)
+    w2 = (model.fc2.weight * s.view(-1, 1)).contiguous()
+    b2 = (model.fc2.bias * s + t).contiguous()
+    d = lambda p: p.detach().clone()  # noqa: E731
+    return FoldedDCNN(N, conv_w, conv_b, w1, b1, w2, b2, d(model.fc3.weight), d(model.fc3.bias),
+                      d(model.fc4.weight), d(model.fc4.bias))
+
+
+def dcnn_fullframe_forward(folded: FoldedDCNN, obs: torch.Tensor, normalize: bool = True, features: bool = False):
+    """DCNNet.eval()'s function the way the device path computes it, in pure torch: all four
+    convolutions as pad-1 convolutions on the full N x N frame, then the interior [2:N-2, 2:N-2] of
+    the fourth output in (r, col, c) order into the folded fc1. Exact, not approximate: the valid
+    outputs of conv3 and conv4 read interior positions of their inputs only, so the border ring
+    (which differs from the valid form) is never read. Returns (log-probs or, normalize=False, raw
+    logits; v), or with features=True (the 64 features after fc2, v)."""
+    f, N = folded, folded.N
+    x = obs
+    for w, b in zip(f.conv_w, f.conv_b):
+        x = F.relu(F.conv2d(x, w, b, padding=1))
+    x = x[:, :, 2:N - 2, 2:N - 2].permute(0, 2, 3, 1).reshape(x.shape[0], -1)
+    x = F.relu(F.linear(x, f.fc1_w, f.fc1_b))
+    x = F.relu(F.linear(x, f.fc2_w, f.fc2_b))
+    v = torch.tanh(F.linear(x, f.fc4_w, f.fc4_b))
+    if features:
+        return x, v
+    logits = F.linear(x, f.fc3_w, f.fc3_b)
+    return (F.log_softmax(logits, dim=1) if normalize else logits), v
+
+
+def conv128_pack(w: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """[128, 128, 3, 3] f32 device weights -> bk_conv128_x3's operands (bk_conv7_pack: the split
+    f16 fragments [bk_conv7_weight_bytes()] uint8 and the inverse row scales [128] f32; they do
+    not depend on the board size)."""
+    from .engine import _check, _ptr, _stream, load_library
+
+    lib = load_library()
+    w = w.detach().float().contiguous()
+    if tuple(w.shape) != (128, 128, 3, 3) or not w.is_cuda:
+        raise ValueError(f"conv128_pack takes a [128, 128, 3, 3] device tensor, got {tuple(w.shape)}")
+    ws = torch.empty(lib.bk_conv7_weight_bytes(), dtype=torch.uint8, device=w.device)
+    inv = torch.empty(128, dtype=torch.float32, device=w.device)
+    _check(lib.bk_conv7_pack(_ptr(w), 0, _ptr(ws), _ptr(inv), _stream(w.device)))
+    return ws, inv
+
+
+def _nhwc128(t: torch.Tensor, what: str) -> tuple[int, int]:
+    if (t.dim() != 4 or t.shape[1] != t.shape[2] or t.shape[3] != 128 or t.dtype != torch.float32 or not t.is_cuda
+            or not t.is_contiguous()):
+        raise ValueError(f"{what}: a contiguous [B, N, N, 128] f32 device tensor, got {tuple(t.shape)} {t.dtype}")
+    return t.shape[0], t.shape[1]
+
+
+def conv128_x3(x: torch.Tensor, ws: torch.Tensor, inv: torch.Tensor, bias: torch.Tensor | None, relu: bool = False,
+               out: torch.Tensor | None = None) -> torch.Tensor:
+    """bk_conv128_x3: the 128 -> 128 3x3 pad-1 convolution of an NHWC activation [B, N, N, 128] f32
+    (N = 7, 14 or 20) on split-f16 MFMA products, + bias, optional ReLU -> [B, N, N, 128] (into
+    `out` when given)."""
+    from .engine import _check, _ptr, _stream, load_library
+
+    B, N = _nhwc128(x, "conv128_x3")
+    y = torch.empty_like(x) if out is None else out
+    if out is not None and (_nhwc128(out, "conv128_x3 out") != (B, N) or out.data_ptr() == x.data_ptr()):
+        raise ValueError("conv128_x3: out must be another tensor of x's shape")
+    _check(load_library().bk_conv128_x3(_ptr(x), B, N, _ptr(ws), _ptr(inv), _ptr(bias), int(relu), _ptr(y),
+                                        _stream(x.device)))
+    return y
+
+
+def conv128_first(obs: torch.Tensor, w: torch.Tensor, bias: torch.Tensor | None, relu: bool = False,
+                  out: torch.Tensor | None = None) -> torch.Tensor:
+    """bk_conv128_first: the planar observation [B, cin, N, N] f32 (cin = 4, 6 or 8; N = 7, 14 or
+    20) through the 3x3 pad-1 convolution w [128, cin, 3, 3] (or flattened [128, cin * 9]) in fp32
+    with a fixed summation order, + bias, optional ReLU -> NHWC [B, N, N, 128]."""
+    from .engine import _check, _ptr, _stream, load_library
+
+    if obs.dim() != 4 or obs.shape[2] != obs.shape[3] or obs.dtype != torch.float32 or not obs.is_cuda:
+        raise ValueError(f"conv128_first: a [B, cin, N, N] f32 device tensor, got {tuple(obs.shape)} {obs.dtype}")
+    B, cin, N, _ = obs.shape
+    if w.dtype != torch.float32 or w.numel() != 128 * cin * 9 or not w.is_contiguous():
+        raise ValueError(f"conv128_first: contiguous f32 weights [128, {cin}, 3, 3], got {tuple(w.shape)} {w.dtype}")
+    obs = obs.contiguous()
+    y = torch.empty((B, N, N, 128), dtype=torch.float32, device=obs.device) if out is None else out
+    if out is not None and _nhwc128(out, "conv128_first out") != (B, N):
+        raise ValueError("conv128_first: out must be [B, N, N, 128]")
+    _check(load_library().bk_conv128_first(_ptr(obs), B, N, cin, _ptr(w), _ptr(bias), int(relu), _ptr(y),
+                                           _stream(obs.device)))
+    return y
+
+
+class LeafDCNNet(nn.Module):
+    """The leaf evaluator's DCNNet on the device (fp32): dcnn_fullframe_forward with conv1 as one
+    bk_conv128_first launch on the planar observation [B, 2P, N, N] (as the search writes it) and
+    conv2..conv4 as bk_conv128_x3 launches (split-f16 MFMA products, fp32-class) over two NHWC
+    activation buffers per batch size (allocated at the first call with that batch size, so a
+    captured forward allocates none of them); the crop, fc1, fc2 and fc4 stay on PyTorch (one addmm
+    each). features=True returns (the 64 features after fc2, v) and leaves fc3 to the search's
+    sparse policy head (sparse_head()); otherwise (log-probs or, normalize=False, raw logits; v).
+
+    It qualifies when the net has 128 channels, 4, 6 or 8 input planes, a 7x7, 14x14 or 20x20 board
+    and fp32 parameters on a HIP device. A net that does not keeps the cause in `reason` and
+    forward runs model.eval() itself (the same outputs, whatever normalize / features say).
+
+    There is no packed-state entry: takes_states() is False, so self-play feeds it observation
+    planes and runs its simulations as one chain (no pipelined tree groups)."""
+
+    def __init__(self, model: DCNNet, normalize: bool = True, features: bool = False):
+        super().__init__()
+        self.model = model.eval()
+        self.normalize = normalize
+        self.features = features
+        self.N, self.cin = model.board_x, model.conv1.in_channels
+        p = model.conv1.weight
+        self.reason = None
+        if model.num_channels != 128:
+            self.reason = f"{model.num_channels} channels (the split-f16 kernels take 128)"
+        elif self.cin not in (4, 6, 8):
+            self.reason = f"{self.cin} input planes (4, 6 or 8)"
+        elif self.N not in (7, 14, 20):
+            self.reason = f"{self.N}x{self.N} board (7x7, 14x14 or 20x20)"
+        elif p.dtype != torch.float32:
+            self.reason = f"{p.dtype} parameters (float32)"
+        elif p.device.type != "cuda":
+            self.reason = f"parameters on {p.device.type} (a HIP device)"
+        self.native = self.reason is None
+        self._act = {}  # batch size -> the two NHWC activation buffers
+        if not self.native:
+            return
+        f = fold_dcnn(model)
+        # (2-D / 1-D buffers: a later .to(memory_format=channels_last) leaves their layout alone)
+        self.register_buffer("w_first", f.conv_w[0].reshape(128, -1).contiguous())
+        for i in range(4):
+            self.register_buffer(f"b_conv{i}", f.conv_b[i])
+        for i in (1, 2, 3):
+            ws, inv = conv128_pack(f.conv_w[i])
+            self.register_buffer(f"ws_conv{i}", ws)
+            self.register_buffer(f"inv_conv{i}", inv)
+        self.register_buffer("fc1_wt", f.fc1_w.t().contiguous())
+        self.register_buffer("fc1_b", f.fc1_b)
+        self.register_buffer("fc2_wt", f.fc2_w.t().contiguous())
+        self.register_buffer("fc2_b", f.fc2_b)
+        self.register_buffer("fc4_wt", f.fc4_w.t().contiguous())
+        self.register_buffer("fc4_b", f.fc4_b.contiguous())
+
+    @property
+    def planar_input(self) -> bool:
+        """Whether forward reads the planar observation as the search writes it."""
+        return self.native
+
+    def sparse_head(self):
+        """The Linear (fc3) the search's sparse policy head applies to the features, or None."""
+        return self.model.fc3 if self.native else None
+
+    def takes_states(self) -> bool:
+        return False
+
+    def _activations(self, B: int, device):
+        key = (B, str(device))
+        if key not in self._act:
+            self._act[key] = tuple(torch.empty((B, self.N, self.N, 128), dtype=torch.float32, device=device)
+                                   for _ in range(2))
+        return self._act[key]
+
+    @torch.no_grad()
+    def forward(self, x):
+        if not self.native:
+            return self.model(x)
+        N, cin = self.N, self.cin
+        if x.dim() != 4 or tuple(x.shape[1:]) != (cin, N, N) or not x.is_cuda:
+            raise ValueError(f"LeafDCNNet takes a [B, {cin}, {N}, {N}] device tensor, got {tuple(x.shape)}")
+        B = x.shape[0]
+        src, dst = self._activations(B, x.device)
+        conv128_first(x.float(), self.w_first, self.b_conv0, True, out=src)
+        for i in (1, 2, 3):
+            conv128_x3(src, getattr(self, f"ws_conv{i}"), getattr(self, f"inv_conv{i}"), getattr(self, f"b_conv{i}"),
+                       True, out=dst)
+            src, dst = dst, src
+        h = src[:, 2:N - 2, 2:N - 2, :].reshape(B, -1)  # the valid frame, (r, col, c) order
+        h = torch.relu(torch.addmm(self.fc1_b, h, self.fc1_wt))
+        h = torch.relu(torch.addmm(self.fc2_b, h, self.fc2_wt))
+        v = torch.tanh(torch.addmm(self.fc4_b, h, self.fc4_wt))
+        if self.features:
+            return h, v
+        logits = self.model.fc3(h)
+        return (F.log_softmax(logits, dim=1) if self.normalize else logits), v
+
+
 def inference_model(model: nn.Module, normalize: bool = True, dtype: torch.dtype = torch.float32,
-                    features: bool = False, x3_boards: str | None = None) -> nn.Module:
+                    features: bool = False, x3_boards: str | None = None, dcnn_leaf: str | None = None) -> nn.Module:
     """The leaf evaluator's form of a net: ResNet -> LeafResNet (fp32 HIP kernels) on a HIP
-    device, FusedResNet for reduced-precision autocast runs or off the device; eval() otherwise.
-    normalize=False lets LeafResNet return raw policy logits (see LeafResNet)."""
+    device, FusedResNet for reduced-precision autocast runs or off the device; DCNNet ->
+    LeafDCNNet with dcnn_leaf / BK_DCNN_LEAF "x3" in fp32; eval() otherwise.
+    normalize=False lets LeafResNet / LeafDCNNet return raw policy logits (see LeafResNet)."""
     if isinstance(model, ResNet):
         dev = next(model.parameters()).device
         if dev.type == "cuda" and dtype == torch.float32:
             return LeafResNet(model, normalize=normalize, features=features, x3_boards=x3_boards).eval()
         return FusedResNet(model).eval()
+    if isinstance(model, DCNNet) and dcnn_leaf_mode(dcnn_leaf) == "x3" and dtype == torch.float32:
+        return LeafDCNNet(model, normalize=normalize, features=features).eval()
     return model.eval()

@@ -443,6 +443,28 @@ int bk_dropout_keep(const int64_t* key, int64_t n_pixels, float p, uint32_t* kee
  * (y > 0 implies kept); n floats, a multiple of 4. */
 int bk_conv7_act_grad(const float* gy, const float* y, int64_t n, float keep_scale, float* dz, void* stream);
 
+/* ---------------------------------------------------------------- DCNNet's convolutions (leaf net)
+ * models/blokus_nnet.py:9-85 with 128 channels for the leaf evaluator (conv128.hip). Activations
+ * are NHWC f32 [B][N][N][128], 16-byte aligned.
+ *
+ * bk_conv128_x3: the 128 -> 128 3x3 pad-1 conv on split-f16 MFMA products (bk_conv7's arithmetic,
+ * fp32-class; every board with its own power-of-two scale, so a board's result depends neither on
+ * its batch nor on its tile neighbours) for N = 14 and 20; N = 7 runs bk_conv7 without a keep
+ * mask. y = conv(x) + bias, then, when relu != 0, y = max(y, 0); bias may be NULL. wsplit and inv
+ * come from bk_conv7_pack (flip = 0). bk_conv128_x3_supported(N): 1 for N in {7, 14, 20};
+ * bk_conv128_x3_tile_boards(N): the boards that share one workgroup tile (0: N not supported).
+ *
+ * bk_conv128_first: the first layer on the planar observation obs [B][cin][N][N] f32 (cin = 4, 6
+ * or 8, N = 7, 14 or 20; bk_observe's layout), w [128][cin][3][3] f32, in fp32 with a fixed
+ * summation order (taps outer, input channels inner), + bias (may be NULL), optional ReLU; y NHWC.
+ * B = 0 returns BK_OK; every launch goes on `stream` (capturable). */
+int bk_conv128_x3_supported(int N);
+int bk_conv128_x3_tile_boards(int N);
+int bk_conv128_x3(const float* x, int B, int N, const void* wsplit, const float* inv, const float* bias, int relu,
+                  float* y, void* stream);
+int bk_conv128_first(const float* obs, int B, int N, int cin, const float* w, const float* bias, int relu, float* y,
+                     void* stream);
+
 /* ---------------------------------------------------------------- leaf-evaluator epilogue
  * The conv epilogues of the inference ResNet (models/blokus_nnet.py:135-151, BN folded):
  * in place on x[n] (NHWC, C channels innermost): x = act(x + bias[c] (+ residual)), act = ReLU
