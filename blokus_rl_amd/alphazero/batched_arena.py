@@ -215,7 +215,8 @@ class BatchedArena:
         for m in models:
             ev = LeafEvaluator(m, self.eng, 1, self.nn_dtype, use_graph=False, sparse_policy=True,
                                x3_boards=self.x3_boards if self.x3_boards is not None else getattr(m, "x3_boards", None))
-            if not ev.takes_states:
+            # (the net table is the ResNet's: a DCNNet that takes states has no bk_leafnet_args form)
+            if not (ev.takes_states and getattr(ev.model, "pipelines", False)):
                 self.path_reason = (f"{type(m).__name__} seat: no packed-state split-f16 leaf net for it "
                                     f"({self.eng.N}x{self.eng.N}, {self.eng.P} players, x3_boards / BK_NET_MATH)")
                 return None

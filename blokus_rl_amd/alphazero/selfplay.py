@@ -125,9 +125,10 @@ class LeafEvaluator:
 
     @property
     def takes_states(self) -> bool:
-        """Whether forward_states runs the packed-state leaf kernel (bk_leafnet_x3_states): the sparse
-        HIP ResNet in fp32 with x3 math at a board size the kernel covers. Otherwise forward_states
-        observes the states and runs the planar forward."""
+        """Whether forward_states runs a packed-state leaf kernel: the sparse HIP ResNet in fp32 with
+        x3 math at a board size the kernel covers (bk_leafnet_x3_states), or a native LeafDCNNet
+        under dcnn_leaf "fused" (bk_conv128_first_states). Otherwise forward_states observes the
+        states and runs the planar forward."""
         return bool(self.sparse and self.dtype == torch.float32 and self.model.takes_states())
 
     def forward_states(self, states, status: torch.Tensor | None = None):
@@ -189,7 +190,9 @@ class SelfPlay:
         # x3_boards / BK_X3_BOARDS "all": the one-launch split-f16 leaf net (and with it leaf_input
         # "states" and the pipelined groups) also for 2- and 3-player nets and 7x7 boards
         # dcnn_leaf / BK_DCNN_LEAF "x3": a DCNNet on the split-f16 convolutions with the sparse policy
-        # head (nets.LeafDCNNet; it takes no packed states: leaf_input "planes", one tree group)
+        # head (nets.LeafDCNNet; it takes no packed states: leaf_input "planes", one tree group);
+        # "fused": that with the heads on bk_dcnn_heads and a packed-state first layer, so
+        # leaf_input "states" is honoured (still one tree group)
         self.evaluator = LeafEvaluator(model, eng, games, nn_dtype, use_graph, x3_boards=x3_boards,
                                        dcnn_leaf=dcnn_leaf)
         self._use_graph = use_graph
@@ -214,8 +217,10 @@ class SelfPlay:
         if k not in (1, 2, 4):
             raise ValueError(f"sim_groups / BK_SIM_GROUPS must be 1, 2 or 4, got {k}")
         ev = self.evaluator
-        pipelined = (ev.sparse and ev.dtype == torch.float32 and ev.model.takes_states()
-                     and games >= max(sim_groups_min_games, k))
+        # (the groups' net launch is the ResNet's bk_leafnet_args form: `pipelines`; a DCNNet that
+        # takes states keeps one group)
+        pipelined = (ev.sparse and ev.dtype == torch.float32 and getattr(ev.model, "pipelines", False)
+                     and ev.model.takes_states() and games >= max(sim_groups_min_games, k))
         self.sim_groups = k if pipelined else 1
         ring = sim_ring if sim_ring is not None else os.environ.get("BK_SIM_RING")
         self.sim_ring = int(ring) if ring is not None else (1 if self.sim_groups == 2 else 2)

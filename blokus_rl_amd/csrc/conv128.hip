@@ -1,7 +1,9 @@
 // conv128.hip — DCNNet's convolutions for the leaf evaluator (nets.LeafDCNNet): the 128 -> 128
 // 3x3 pad-1 layers at 14x14 and 20x20 on split-f16 MFMA products (k_conv7_x3's scheme and
 // arithmetic, ppoconv.hip, on another tile geometry; 7x7 is k_conv7_x3 itself), and the first
-// layer (2P input planes -> 128) in plain fp32. Activations are NHWC f32 [B][N][N][128].
+// layer (2P input planes -> 128) in plain fp32, from the planar observation (k_conv128_first) or
+// from the packed states themselves (k_conv128_first_states, the same bits). Activations are NHWC
+// f32 [B][N][N][128].
 //
 // k_conv128_x3<N>: persistent, one workgroup of 4 waves per CU walking tiles of T boards (N = 14:
 // 2 boards = 392 pixels, N = 20: 1 board = 400 pixels; 25 MFMA column groups of 16 either way, so
@@ -386,6 +388,136 @@ __global__ __launch_bounds__(256) void k_conv128_first(const float* __restrict__
   }
 }
 
+// ---- the first layer from packed states: k_conv128_first's sums on the observation planes of
+// states [B][kStateWords] (k_observe, env.hip: plane c < P at (r, col) = bit col of word c kMaxN + r,
+// plane P + q = all ones iff q == the to-move word) without the planes. The inputs are 0 or 1 and
+// fmaf(w, 1, a) = a + w, fmaf(w, 0, a) = a for finite w (a is never -0: it starts at +0), so the
+// terms of zero inputs are left out and the bits equal k_conv128_first's. A wave takes one board
+// row at a time (items strided over all waves): its 3 P row words, shifted up one bit so that bit 0
+// and the bits from N + 1 are the zero halo, and the to-move word sit in scalar registers; a lane
+// owns two output channels, whose 9 P piece weights and the 9 weights of the to-move plane it keeps
+// in registers (from a transposed LDS copy), so a pixel costs 9 packed fmas for the to-move
+// plane, P more for each occupied tap, and one 512-byte row of the NHWC store per wave.
+// (Shifts: the words hold bits 0..N + 1 <= 21; the furthest one read is N - 1 + 2 + 3 <= 24.)
+constexpr int kC128StatesPx = 4;
+// bit `pos` of a (wave-uniform) word as 0.0f or 1.0f
+__device__ __forceinline__ float bit_one(uint32_t word, int pos) {
+  return __builtin_bit_cast(float, ((word >> pos) & 1u) * 0x3f800000u);
+}
+template <int P>
+__global__ __launch_bounds__(256) void k_conv128_first_states(const uint32_t* __restrict__ states,
+                                                              const int32_t* __restrict__ status,
+                                                              const float* __restrict__ w,
+                                                              const float* __restrict__ bias, int relu,
+                                                              float* __restrict__ y, int N, int B) {
+  constexpr int CIN = 2 * P, K = 9 * CIN, NIT = K / 2, RSW = 130;
+  // the weights transposed, [r = c * 9 + tap][o], last row = bias; row stride 130: a wave's writes
+  // (consecutive r) step two banks. Every thread's NIT loads are in flight before the first write.
+  __shared__ __attribute__((aligned(16))) float wt[K + 1][RSW];
+  {
+    float tmp[NIT];
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) tmp[it] = w[it * 256 + threadIdx.x];
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+      const int i = it * 256 + threadIdx.x, o = i / K, r = i - o * K;  // w[o][c][t] = w[o][r]
+      wt[r][o] = tmp[it];
+    }
+  }
+  if (threadIdx.x < 128) wt[K][threadIdx.x] = bias ? bias[threadIdx.x] : 0.0f;
+  __syncthreads();
+  const int oc = 2 * (threadIdx.x & 63);
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  f32x2 wp[9][P];
+#pragma unroll
+  for (int t = 0; t < 9; ++t)
+#pragma unroll
+    for (int c = 0; c < P; ++c) wp[t][c] = *reinterpret_cast<const f32x2*>(&wt[c * 9 + t][oc]);
+  const f32x2 bv = *reinterpret_cast<const f32x2*>(&wt[K][oc]);
+  const uint32_t rowmask = ((1u << N) - 1u) << 1;
+  const int nitems = B * N;
+  for (int item = blockIdx.x * 4 + wave; item < nitems; item += gridDim.x * 4) {
+    const int b = item / N, r = item - b * N;
+    uint32_t rw[3][P], occ[3], inb[3];
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+      occ[d] = inb[d] = 0u;
+#pragma unroll
+      for (int c = 0; c < P; ++c) rw[d][c] = 0u;
+    }
+    int tm = -1;
+    if (!status || status[b] == 1) {  // (wave-uniform) other rows: the all-zero observation, no state read
+      const uint32_t* s = states + (size_t)b * kStateWords;
+      tm = (int)s[kWToMove];
+#pragma unroll
+      for (int d = 0; d < 3; ++d) {
+        const int rr = r + d - 1;
+        if (rr < 0 || rr >= N) continue;
+#pragma unroll
+        for (int c = 0; c < P; ++c) {
+          rw[d][c] = (s[c * kMaxN + rr] << 1) & rowmask;
+          occ[d] |= rw[d][c];
+        }
+        inb[d] = rowmask;
+      }
+    }
+    const bool has_tm = tm >= 0 && tm < P;
+    f32x2 wm[9];
+#pragma unroll
+    for (int t = 0; t < 9; ++t)
+      wm[t] = has_tm ? *reinterpret_cast<const f32x2*>(&wt[(P + tm) * 9 + t][oc]) : f32x2{0.f, 0.f};
+    if (!has_tm) inb[0] = inb[1] = inb[2] = 0u;
+    float* yrow = y + (size_t)item * N * 128 + oc;
+    // kC128StatesPx pixels at a time: their fma chains are independent (each one in
+    // k_conv128_first's order), so they overlap; a tap's piece planes are skipped when none of the
+    // pixels has a piece there. The columns past N - 1 of the last step read halo bits (zeros) and
+    // are not stored.
+    for (int col = 0; col < N; col += kC128StatesPx) {
+      f32x2 a[kC128StatesPx];
+#pragma unroll
+      for (int j = 0; j < kC128StatesPx; ++j) a[j] = f32x2{0.f, 0.f};
+#pragma unroll
+      for (int t = 0; t < 9; ++t) {
+        const int d = t / 3, sh = col + t % 3;
+        constexpr uint32_t kPxMask = (1u << kC128StatesPx) - 1u;
+        if ((occ[d] >> sh) & kPxMask) {
+#pragma unroll
+          for (int c = 0; c < P; ++c) {
+            if (!((rw[d][c] >> sh) & kPxMask)) continue;  // (wave-uniform) this plane is empty under all the pixels
+#pragma unroll
+            for (int j = 0; j < kC128StatesPx; ++j) {
+              const float xv = bit_one(rw[d][c], sh + j);
+              a[j].x = fmaf(wp[t][c].x, xv, a[j].x);
+              a[j].y = fmaf(wp[t][c].y, xv, a[j].y);
+            }
+          }
+        }
+        if (((inb[d] >> sh) & kPxMask) == kPxMask) {  // (wave-uniform) the tap is on the board for all the pixels
+#pragma unroll
+          for (int j = 0; j < kC128StatesPx; ++j) a[j] = pk_add(a[j], wm[t]);  // = fmaf(w, 1, a)
+        } else {
+#pragma unroll
+          for (int j = 0; j < kC128StatesPx; ++j) {
+            const float xm = bit_one(inb[d], sh + j);
+            a[j].x = fmaf(wm[t].x, xm, a[j].x);
+            a[j].y = fmaf(wm[t].y, xm, a[j].y);
+          }
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < kC128StatesPx; ++j) {
+        if (col + j >= N) break;
+        f32x2 v{a[j].x + bv.x, a[j].y + bv.y};
+        if (relu) {
+          v.x = max_bits(v.x, 0);
+          v.y = max_bits(v.y, 0);
+        }
+        *reinterpret_cast<f32x2*>(yrow + (size_t)(col + j) * 128) = v;
+      }
+    }
+  }
+}
+
 __host__ inline bool a16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
 template <int N>
@@ -446,6 +578,27 @@ int bk_conv128_first(const float* obs, int B, int N, int cin, const float* w, co
   else
     hipLaunchKernelGGL(k_conv128_first<8>, grid, dim3(256), 0, s, obs, w, bias, relu, y, N, npx);
   return launch_check("k_conv128_first");
+}
+
+int bk_conv128_first_states(const void* states, const int32_t* status, int B, int N, int P, const float* w,
+                            const float* bias, int relu, float* y, void* stream) {
+  BK_REQUIRE(w && B >= 0 && (B == 0 || (states && y)), "bad argument");
+  BK_REQUIRE(N == 7 || N == 14 || N == 20, "bk_conv128_first_states: board size must be 7, 14 or 20");
+  BK_REQUIRE(P >= 2 && P <= 4, "bk_conv128_first_states: 2, 3 or 4 players");
+  BK_REQUIRE(a16(y) && ((uintptr_t)states & 3u) == 0, "bk_conv128_first_states: aligned buffers");
+  BK_REQUIRE((long long)B * N <= 0x7fff0000LL, "bk_conv128_first_states: batch too large");
+  if (B == 0) return BK_OK;
+  const int items = B * N, g = (items + 3) / 4;  // one board row per wave and step
+  const dim3 grid((unsigned)(g > 1024 ? 1024 : g));  // 4 resident workgroups per CU, each transposing the weights once
+  hipStream_t s = (hipStream_t)stream;
+  const uint32_t* st = (const uint32_t*)states;
+  if (P == 2)
+    hipLaunchKernelGGL(k_conv128_first_states<2>, grid, dim3(256), 0, s, st, status, w, bias, relu, y, N, B);
+  else if (P == 3)
+    hipLaunchKernelGGL(k_conv128_first_states<3>, grid, dim3(256), 0, s, st, status, w, bias, relu, y, N, B);
+  else
+    hipLaunchKernelGGL(k_conv128_first_states<4>, grid, dim3(256), 0, s, st, status, w, bias, relu, y, N, B);
+  return launch_check("k_conv128_first_states");
 }
 
 }  // extern "C"

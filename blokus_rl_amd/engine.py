@@ -116,6 +116,12 @@ _SIGS = {
     "bk_conv128_x3_tile_boards": (_i, [_i]),
     "bk_conv128_x3": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp]),
     "bk_conv128_first": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp]),
+    "bk_conv128_first_states": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp]),
+    "bk_dcnn_heads_supported": (_i, [_i]),
+    "bk_dcnn_heads_slices": (_i, [_i]),
+    "bk_dcnn_heads_weight_floats": (_i, [_i]),
+    "bk_dcnn_heads_pack": (_i, [_vp, _i, _vp, _vp]),
+    "bk_dcnn_heads": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "bk_bias_act": (_i, [_vp, ctypes.c_int64, _i, _vp, _vp, _i, _vp]),
     "bk_conv3x3_packed_floats": (_i, [_i]),
     "bk_conv3x3_form": (_i, [_i, _i]),

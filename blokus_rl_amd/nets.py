@@ -7,7 +7,8 @@ semantics and `state_dict` keys follow the reference so its checkpoints load unc
   1x1 conv(2)+BN+ReLU+Linear(2*N*N -> A)+log_softmax, value head 1x1 conv(1)+BN+ReLU+
   Linear(N*N -> 64)+ReLU+Linear(64 -> P)+tanh.
 * `DCNNet`  — blokus_nnet.py:9-85; as a leaf net optionally `LeafDCNNet` (dcnn_leaf / BK_DCNN_LEAF "x3":
-  the convolutions on csrc/conv128.hip, the sparse policy head).
+  the convolutions on csrc/conv128.hip, the sparse policy head; "fused": also the heads on
+  csrc/dcnnheads.hip and the first layer from packed states).
 * `DumbNet` — models/dumbnet.py:6-21: logits 1, value 0 (the "uninformed MCTS" opponent).
 """
 from __future__ import annotations
@@ -706,6 +707,8 @@ class LeafResNet(nn.Module):
     comes back as raw logits (the leaf batch's consumer, k_expand_backup, takes a softmax over the
     legal ids, which a per-row shift does not change), skipping the full-row log-softmax."""
 
+    pipelines = True  # takes_states() comes with a bk_leafnet_args form (leafnet_x3_args / leafnet_x3_table)
+
     def __init__(self, net: ResNet, normalize: bool = True, features: bool = False, x3_boards: str | None = None):
         super().__init__()
         # "all": the one-launch split-f16 net also for 2- and 3-player stems and 7x7 boards
@@ -884,13 +887,14 @@ class LeafResNet(nn.Module):
 
 def dcnn_leaf_mode(arg: str | None = None) -> str:
     """How a DCNNet evaluates the leaf batch: "torch" (default) = model.eval() on PyTorch, "x3" =
-    LeafDCNNet (the convolutions on the split-f16 MFMA kernels, the sparse policy head). arg, else
-    BK_DCNN_LEAF."""
+    LeafDCNNet (the convolutions on the split-f16 MFMA kernels, the sparse policy head), "fused" =
+    LeafDCNNet(fused=True): x3 with the heads on bk_dcnn_heads and a packed-state entry
+    (bk_conv128_first_states). arg, else BK_DCNN_LEAF."""
     import os
 
     m = arg if arg is not None else os.environ.get("BK_DCNN_LEAF", "torch")
-    if m not in ("torch", "x3"):
-        raise ValueError(f"dcnn_leaf / BK_DCNN_LEAF must be torch or x3, got {m!r}")
+    if m not in ("torch", "x3", "fused"):
+        raise ValueError(f"dcnn_leaf / BK_DCNN_LEAF must be torch, x3 or fused, got {m!r}")
     return m
 
 
@@ -1016,6 +1020,90 @@ def conv128_first(obs: torch.Tensor, w: torch.Tensor, bias: torch.Tensor | None,
     return y
 
 
+def conv128_first_states(states, status: torch.Tensor | None, N: int, P: int, w: torch.Tensor,
+                         bias: torch.Tensor | None, relu: bool = False, out: torch.Tensor | None = None) -> torch.Tensor:
+    """bk_conv128_first_states: conv128_first on the observation planes of packed states [B, 384]
+    uint8 (P players on an N x N board; w [128, 2P, 3, 3] or flattened) without the planes, bitwise
+    the same -> NHWC [B, N, N, 128]. status [B] int32 or None: rows whose status is not 1 are
+    evaluated as the all-zero observation and their state bytes are not read. states may also be
+    the device address (int) of a [B, 384] buffer the caller keeps alive
+    (BatchedMCTS.leaf_states_ptr), with B = len(status)."""
+    from .engine import STATE_BYTES, _check, _ptr, _stream, load_library
+
+    dev = w.device
+    if isinstance(states, torch.Tensor):
+        if (states.dtype != torch.uint8 or states.dim() != 2 or states.shape[1] != STATE_BYTES
+                or not states.is_contiguous() or states.device != dev):
+            raise ValueError(f"conv128_first_states: contiguous [B, {STATE_BYTES}] uint8 states on {dev}")
+        B, sptr = states.shape[0], ctypes.c_void_p(states.data_ptr())
+    else:
+        if status is None:
+            raise ValueError("conv128_first_states: a raw states address needs status for the batch size")
+        B, sptr = status.shape[0], ctypes.c_void_p(int(states))
+    if status is not None and (status.dtype != torch.int32 or tuple(status.shape) != (B,) or not status.is_contiguous()
+                               or status.device != dev):
+        raise ValueError("conv128_first_states: status must be a contiguous [B] int32 tensor on the weights' device")
+    if w.dtype != torch.float32 or w.numel() != 128 * 2 * P * 9 or not w.is_contiguous() or not w.is_cuda:
+        raise ValueError(f"conv128_first_states: contiguous f32 device weights [128, {2 * P}, 3, 3], "
+                         f"got {tuple(w.shape)} {w.dtype}")
+    y = torch.empty((B, N, N, 128), dtype=torch.float32, device=dev) if out is None else out
+    if out is not None and _nhwc128(out, "conv128_first_states out") != (B, N):
+        raise ValueError("conv128_first_states: out must be [B, N, N, 128]")
+    _check(load_library().bk_conv128_first_states(sptr, _ptr(status), B, N, P, _ptr(w), _ptr(bias), int(relu),
+                                                  _ptr(y), _stream(dev)))
+    return y
+
+
+class DCNNHeads:
+    """bk_dcnn_heads' operands from a FoldedDCNN (fp32, on a HIP device): fc1's weights in the
+    kernel's fragment order (bk_dcnn_heads_pack), the transposed fc2 / fc4 weights, the biases, and
+    the partial-sum workspaces, kept per batch size (allocated at the first call with that batch
+    size, so a captured call allocates none)."""
+
+    def __init__(self, f: FoldedDCNN):
+        from .engine import _check, _ptr, _stream, load_library
+
+        lib = load_library()
+        w1 = f.fc1_w.detach().float().contiguous()
+        self.N, self.P = f.N, f.fc4_w.shape[0]
+        if not lib.bk_dcnn_heads_supported(self.N) or not w1.is_cuda:
+            raise ValueError(f"DCNNHeads: a {self.N}x{self.N} board on {w1.device} (7x7, 14x14 or 20x20 on a HIP device)")
+        if tuple(w1.shape) != (128, 128 * (self.N - 4) ** 2) or tuple(f.fc2_w.shape) != (64, 128):
+            raise ValueError(f"DCNNHeads: fc1 {tuple(w1.shape)} / fc2 {tuple(f.fc2_w.shape)} are not DCNNet's at 128 channels")
+        self.slices = lib.bk_dcnn_heads_slices(self.N)
+        self.fc1_packed = torch.empty(lib.bk_dcnn_heads_weight_floats(self.N), dtype=torch.float32, device=w1.device)
+        _check(lib.bk_dcnn_heads_pack(_ptr(w1), self.N, _ptr(self.fc1_packed), _stream(w1.device)))
+        c = lambda t: t.detach().float().contiguous().clone()  # noqa: E731
+        self.fc1_b, self.fc2_wt, self.fc2_b = c(f.fc1_b), c(f.fc2_w.t()), c(f.fc2_b)
+        self.fc4_wt, self.fc4_b = c(f.fc4_w.t()), c(f.fc4_b)
+        self._ws = {}
+
+    def tensors(self):
+        return [self.fc1_packed, self.fc1_b, self.fc2_wt, self.fc2_b, self.fc4_wt, self.fc4_b]
+
+    def workspace(self, B: int, device) -> torch.Tensor:
+        key = (B, str(device))
+        if key not in self._ws:
+            self._ws[key] = torch.empty(max(1, self.slices * B * 128), dtype=torch.float32, device=device)
+        return self._ws[key]
+
+
+def dcnn_heads(x: torch.Tensor, heads: DCNNHeads) -> tuple[torch.Tensor, torch.Tensor]:
+    """bk_dcnn_heads: the fourth convolution's full-frame NHWC output [B, N, N, 128] f32 -> (the 64
+    features after fc2 [B, 64], v [B, P]): the interior [2:N-2, 2:N-2] read in place, fc1 + ReLU,
+    fc2 + ReLU, tanh(fc4). A board's outputs do not depend on its batch (bitwise)."""
+    from .engine import _check, _ptr, _stream, load_library
+
+    B, N = _nhwc128(x, "dcnn_heads")
+    if N != heads.N or x.device != heads.fc1_packed.device:
+        raise ValueError(f"dcnn_heads: a {heads.N}x{heads.N} activation on {heads.fc1_packed.device}, got {N}x{N} on {x.device}")
+    feats = torch.empty((B, 64), dtype=torch.float32, device=x.device)
+    v = torch.empty((B, heads.P), dtype=torch.float32, device=x.device)
+    _check(load_library().bk_dcnn_heads(_ptr(x), B, N, heads.P, *[_ptr(t) for t in heads.tensors()],
+                                        _ptr(heads.workspace(B, x.device)), _ptr(feats), _ptr(v), _stream(x.device)))
+    return feats, v
+
+
 class LeafDCNNet(nn.Module):
     """The leaf evaluator's DCNNet on the device (fp32): dcnn_fullframe_forward with conv1 as one
     bk_conv128_first launch on the planar observation [B, 2P, N, N] (as the search writes it) and
@@ -1029,14 +1117,22 @@ class LeafDCNNet(nn.Module):
     and fp32 parameters on a HIP device. A net that does not keeps the cause in `reason` and
     forward runs model.eval() itself (the same outputs, whatever normalize / features say).
 
-    There is no packed-state entry: takes_states() is False, so self-play feeds it observation
-    planes and runs its simulations as one chain (no pipelined tree groups)."""
+    Without `fused` there is no packed-state entry: takes_states() is False, so self-play feeds it
+    observation planes. fused=True (dcnn_leaf / BK_DCNN_LEAF "fused"): the heads run on
+    bk_dcnn_heads (dcnn_heads: no crop copy, no addmm; its partial sums in a per-batch-size
+    workspace) and forward_states(states, status) runs the first layer on the search's packed states
+    (bk_conv128_first_states, bitwise conv128_first on their planes), so takes_states() holds. Either
+    way self-play runs a DCNNet's simulations as one chain (`pipelines` is False: the pipelined tree
+    groups and the arena's net table are the ResNet's)."""
 
-    def __init__(self, model: DCNNet, normalize: bool = True, features: bool = False):
+    pipelines = False  # no bk_leafnet_args form: SelfPlay's pipelined groups / the arena's table are LeafResNet's
+
+    def __init__(self, model: DCNNet, normalize: bool = True, features: bool = False, fused: bool = False):
         super().__init__()
         self.model = model.eval()
         self.normalize = normalize
         self.features = features
+        self.fused = bool(fused)
         self.N, self.cin = model.board_x, model.conv1.in_channels
         p = model.conv1.weight
         self.reason = None
@@ -1069,6 +1165,7 @@ class LeafDCNNet(nn.Module):
         self.register_buffer("fc2_b", f.fc2_b)
         self.register_buffer("fc4_wt", f.fc4_w.t().contiguous())
         self.register_buffer("fc4_b", f.fc4_b.contiguous())
+        self.heads = DCNNHeads(f) if self.fused else None
 
     @property
     def planar_input(self) -> bool:
@@ -1080,7 +1177,25 @@ class LeafDCNNet(nn.Module):
         return self.model.fc3 if self.native else None
 
     def takes_states(self) -> bool:
-        return False
+        """Whether forward_states runs bk_conv128_first_states (the native fused form)."""
+        return bool(self.native and self.fused)
+
+    @torch.no_grad()
+    def forward_states(self, states, status: torch.Tensor | None = None):
+        """forward on the observation planes of packed states [B, 384] uint8 (or the device address
+        of such a buffer, with B = len(status)), without the planes: the same tuple, bitwise.
+        status [B] int32 or None: rows whose status is not 1 count as the all-zero observation."""
+        if not self.takes_states():
+            if not isinstance(states, torch.Tensor):
+                raise ValueError("LeafDCNNet.forward_states: a raw states address needs the fused native form")
+            obs = _observe_states(states, self.N, self.cin // 2)
+            if status is not None:
+                obs = obs * (status == 1).view(-1, 1, 1, 1).to(obs.dtype)
+            return self.forward(obs)
+        B = states.shape[0] if isinstance(states, torch.Tensor) else status.shape[0]
+        src, dst = self._activations(B, self.w_first.device)
+        conv128_first_states(states, status, self.N, self.cin // 2, self.w_first, self.b_conv0, True, out=src)
+        return self._tail(src, dst)
 
     def _activations(self, B: int, device):
         key = (B, str(device))
@@ -1099,14 +1214,22 @@ class LeafDCNNet(nn.Module):
         B = x.shape[0]
         src, dst = self._activations(B, x.device)
         conv128_first(x.float(), self.w_first, self.b_conv0, True, out=src)
+        return self._tail(src, dst)
+
+    def _tail(self, src, dst):
+        """conv2..conv4 and the heads from the first layer's output in src."""
+        N, B = self.N, src.shape[0]
         for i in (1, 2, 3):
             conv128_x3(src, getattr(self, f"ws_conv{i}"), getattr(self, f"inv_conv{i}"), getattr(self, f"b_conv{i}"),
                        True, out=dst)
             src, dst = dst, src
-        h = src[:, 2:N - 2, 2:N - 2, :].reshape(B, -1)  # the valid frame, (r, col, c) order
-        h = torch.relu(torch.addmm(self.fc1_b, h, self.fc1_wt))
-        h = torch.relu(torch.addmm(self.fc2_b, h, self.fc2_wt))
-        v = torch.tanh(torch.addmm(self.fc4_b, h, self.fc4_wt))
+        if self.fused:
+            h, v = dcnn_heads(src, self.heads)
+        else:
+            h = src[:, 2:N - 2, 2:N - 2, :].reshape(B, -1)  # the valid frame, (r, col, c) order
+            h = torch.relu(torch.addmm(self.fc1_b, h, self.fc1_wt))
+            h = torch.relu(torch.addmm(self.fc2_b, h, self.fc2_wt))
+            v = torch.tanh(torch.addmm(self.fc4_b, h, self.fc4_wt))
         if self.features:
             return h, v
         logits = self.model.fc3(h)
@@ -1117,13 +1240,15 @@ def inference_model(model: nn.Module, normalize: bool = True, dtype: torch.dtype
                     features: bool = False, x3_boards: str | None = None, dcnn_leaf: str | None = None) -> nn.Module:
     """The leaf evaluator's form of a net: ResNet -> LeafResNet (fp32 HIP kernels) on a HIP
     device, FusedResNet for reduced-precision autocast runs or off the device; DCNNet ->
-    LeafDCNNet with dcnn_leaf / BK_DCNN_LEAF "x3" in fp32; eval() otherwise.
+    LeafDCNNet with dcnn_leaf / BK_DCNN_LEAF "x3" or "fused" (LeafDCNNet(fused=True)) in fp32;
+    eval() otherwise.
     normalize=False lets LeafResNet / LeafDCNNet return raw policy logits (see LeafResNet)."""
     if isinstance(model, ResNet):
         dev = next(model.parameters()).device
         if dev.type == "cuda" and dtype == torch.float32:
             return LeafResNet(model, normalize=normalize, features=features, x3_boards=x3_boards).eval()
         return FusedResNet(model).eval()
-    if isinstance(model, DCNNet) and dcnn_leaf_mode(dcnn_leaf) == "x3" and dtype == torch.float32:
-        return LeafDCNNet(model, normalize=normalize, features=features).eval()
+    mode = dcnn_leaf_mode(dcnn_leaf) if isinstance(model, DCNNet) else "torch"
+    if mode != "torch" and dtype == torch.float32:
+        return LeafDCNNet(model, normalize=normalize, features=features, fused=mode == "fused").eval()
     return model.eval()

@@ -85,14 +85,15 @@ class BlokusNNetWrapper:
     def predict_states(self, states: torch.Tensor):
         """predict_batch from packed states: states [G, 384] uint8 on the device -> (logp [G, A] f32,
         v [G, P] f32), equal as float values to predict_batch(Engine.observe(states)). The HIP
-        ResNet reads the states directly (LeafResNet.forward_states: no observation planes); every
+        ResNet reads the states directly (LeafResNet.forward_states: no observation planes), and so
+        does a native LeafDCNNet under BK_DCNN_LEAF=fused (bitwise predict_batch's values); every
         other net observes them first."""
-        from .nets import LeafResNet, _observe_states
+        from .nets import LeafDCNNet, LeafResNet, _observe_states
 
         if self._infer is None:
             self._infer = inference_model(self.model).to(memory_format=torch.channels_last)
         states = states.to(self.device).contiguous()
-        if isinstance(self._infer, LeafResNet):
+        if isinstance(self._infer, LeafResNet) or (isinstance(self._infer, LeafDCNNet) and self._infer.takes_states()):
             lp, v = self._infer.forward_states(states)
             return lp.float().contiguous(), v.float().contiguous()
         return self.predict_batch(_observe_states(states, self.game.board_size, self.game.number_of_players))

@@ -457,6 +457,14 @@ int bk_conv7_act_grad(const float* gy, const float* y, int64_t n, float keep_sca
  * bk_conv128_first: the first layer on the planar observation obs [B][cin][N][N] f32 (cin = 4, 6
  * or 8, N = 7, 14 or 20; bk_observe's layout), w [128][cin][3][3] f32, in fp32 with a fixed
  * summation order (taps outer, input channels inner), + bias (may be NULL), optional ReLU; y NHWC.
+ *
+ * bk_conv128_first_states: bk_conv128_first on the observation planes of packed states
+ * [B][384 bytes] (bk_observe: plane p < P at (r, c) = bit c of word p * 20 + r, plane P + q all ones
+ * iff q == the to-move word) without the planes, P = 2, 3 or 4, w [128][2P][3][3]. status [B] (may
+ * be NULL): a row whose status is not 1 is evaluated as the all-zero observation and its state
+ * bytes are not read (bk_leafnet_x3_np_states' contract). For finite weights y is bitwise
+ * bk_conv128_first's on bk_observe's planes: the inputs are 0 or 1, and the selected weights are
+ * summed in its order.
  * B = 0 returns BK_OK; every launch goes on `stream` (capturable). */
 int bk_conv128_x3_supported(int N);
 int bk_conv128_x3_tile_boards(int N);
@@ -464,6 +472,29 @@ int bk_conv128_x3(const float* x, int B, int N, const void* wsplit, const float*
                   float* y, void* stream);
 int bk_conv128_first(const float* obs, int B, int N, int cin, const float* w, const float* bias, int relu, float* y,
                      void* stream);
+int bk_conv128_first_states(const void* states, const int32_t* status, int B, int N, int P, const float* w,
+                            const float* bias, int relu, float* y, void* stream);
+
+/* ---------------------------------------------------------------- DCNNet's heads (leaf net)
+ * dcnnheads.hip: from the fourth convolution's full-frame NHWC output x [B][N][N][128] (N = 7, 14
+ * or 20; bk_dcnn_heads_supported) to the 64 features after fc2 and v = tanh(fc4), BatchNorm folded:
+ *   h1 = relu(fc1 (interior of x) + fc1_b), fc1: K1 = 128 (N-4)^2 -> 128, its columns in (r, col, c)
+ *        order over the interior [2:N-2, 2:N-2], which is read in place (nothing outside it is read);
+ *   feats [B][64] = relu(h1 fc2_wt + fc2_b), fc2_wt [128][64] (the transposed weight);
+ *   v [B][P] = tanh(feats fc4_wt + fc4_b), fc4_wt [64][P] (transposed), 1 <= P <= 64.
+ * fc1 runs on the exact-f32 MFMA, split along K into bk_dcnn_heads_slices(N) slices (a function of
+ * N only) whose partial sums go to workspace [slices * B * 128 floats] and are added in slice
+ * order: no atomics, and a board's outputs are bitwise the same in any batch and at any place in
+ * it. fc1_packed (bk_dcnn_heads_weight_floats(N) = 128 K1 floats) comes from bk_dcnn_heads_pack
+ * (fc1_w [128][K1] f32). x, fc1_packed and workspace 16-byte aligned. fp32-class accuracy. B = 0
+ * returns BK_OK; two launches on `stream` (capturable), nothing allocated. */
+int bk_dcnn_heads_supported(int N);
+int bk_dcnn_heads_slices(int N);
+int bk_dcnn_heads_weight_floats(int N);
+int bk_dcnn_heads_pack(const float* fc1_w, int N, float* packed, void* stream);
+int bk_dcnn_heads(const float* x, int B, int N, int P, const float* fc1_packed, const float* fc1_b, const float* fc2_wt,
+                  const float* fc2_b, const float* fc4_wt, const float* fc4_b, float* workspace, float* feats,
+                  float* v, void* stream);
 
 /* ---------------------------------------------------------------- leaf-evaluator epilogue
  * The conv epilogues of the inference ResNet (models/blokus_nnet.py:135-151, BN folded):
