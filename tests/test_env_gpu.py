@@ -17,18 +17,36 @@ from oracle.oracle import Oracle
 
 pytestmark = pytest.mark.gpu
 
-PRESETS = [(20, 4, 5), (7, 2, 5), (7, 2, 4)]
+PRESETS = [(20, 4, 5), (7, 2, 5), (7, 2, 4), (14, 4, 5), (14, 2, 5), (20, 2, 5), (20, 4, 4)]
+
+# (preset, max_plies): the board-size sweep of the legal-mask kernel. 64 // N boards per wave:
+# 12, 8, 6, 4, 4, 4, 3, 3, with idle lanes (N = 5, 10, 13, 14, 20) and without (N = 8, 16);
+# max_plies is about the length of a random game of the preset, so boards of every stage occur.
+SWEEP = [((5, 2, 5), 7), ((8, 4, 5), 18), ((10, 2, 5), 21), ((13, 4, 5), 34), ((14, 4, 5), 38),
+         ((16, 4, 5), 48), ((20, 4, 4), 38), ((20, 2, 5), 44)]
+
+
+class _PerPreset(dict):
+    """preset -> object, made on first use."""
+
+    def __init__(self, make):
+        super().__init__()
+        self.make = make
+
+    def __missing__(self, preset):
+        self[preset] = self.make(*preset)
+        return self[preset]
 
 
 @pytest.fixture(scope="module")
 def engines():
     from blokus_rl_amd.engine import Engine
-    return {p: Engine(*p) for p in PRESETS}
+    return _PerPreset(Engine)
 
 
 @pytest.fixture(scope="module")
 def oracles():
-    return {p: Oracle(*p) for p in PRESETS}
+    return _PerPreset(Oracle)
 
 
 def _np(t: torch.Tensor) -> np.ndarray:
@@ -49,9 +67,9 @@ def test_init_states(engines, oracles, preset):
 def test_lockstep_random_games(engines, oracles, preset):
     """B games played to the end with uniform random legal moves; every ply compares the GPU
     engine with the oracle: legal bitmask + count for the mover and for every other colour,
-    next state bytes, next player, terminal flag + scores, observation planes."""
+    next state bytes, next player, terminal flag + scores, observation planes, square counts."""
     eng, o = engines[preset], oracles[preset]
-    B = 24 if preset[0] == 20 else 64
+    B = {20: 24 if preset == (20, 4, 5) else 16, 14: 32, 7: 64}[preset[0]]
     rngs = [np.random.default_rng(1000 + b) for b in range(B)]
     st_g = eng.init_states(B)
     st_o = [o.init_state() for _ in range(B)]
@@ -61,6 +79,7 @@ def test_lockstep_random_games(engines, oracles, preset):
         ended, scores = eng.game_ended(st_g)
         ended_h, scores_h = _np(ended), _np(scores)
         obs_h = _np(eng.observe(st_g))
+        sq_h = _np(eng.square_counts(st_g))
         other = torch.tensor([(ply + b) % o.P for b in range(B)], dtype=torch.int32, device=eng.device)
         m2, c2 = eng.legal_mask(st_g, other)
         m2_h, c2_h = _np(m2).view(np.uint64), _np(c2)
@@ -76,6 +95,7 @@ def test_lockstep_random_games(engines, oracles, preset):
             if ref_scores is not None:
                 assert (scores_h[b] == ref_scores).all()
             assert (obs_h[b] == o.observe(st_o[b])).all()
+            assert (sq_h[b] == o.square_counts(st_o[b])).all(), (ply, b)
             if ref_scores is None:
                 ids = o.legal_ids(st_o[b])
                 acts[b] = int(ids[int(rngs[b].integers(len(ids)))])
@@ -170,12 +190,103 @@ def test_legal_mask_ragged_groups(engines, oracles, B):
     assert int(counts[B]) == -7 and bool((masks[B] == -1).all())
 
 
-def test_hash_is_board_only(engines, oracles):
-    eng, o = engines[(20, 4, 5)], oracles[(20, 4, 5)]
+@pytest.fixture(scope="module")
+def sweep_boards(oracles):
+    """preset -> the 5 * bpw + 2 oracle boards of the sweep (host, read-only)."""
+    def make(N, P, maxc):
+        o, max_plies = oracles[(N, P, maxc)], dict(SWEEP)[(N, P, maxc)]
+        st = np.stack([o.random_board(300 + b, max_plies) for b in range(5 * (64 // N) + 2)])
+        st.setflags(write=False)
+        return st
+    return _PerPreset(make)
+
+
+@pytest.mark.parametrize("preset", [p for p, _ in SWEEP], ids=lambda p: "x".join(map(str, p)))
+def test_board_size_sweep(engines, oracles, sweep_boards, preset):
+    """k_legal_mask_rows at every boards-per-wave geometry (bpw = 64 // N), on batches of one board,
+    one short of a wave, a full wave, one over and five waves plus two: masks and counts of the
+    mover and of every colour, nothing written past the last board; and on the same mid-game oracle
+    boards legal_ids, next_state of one random legal action per board (state bytes with the hash,
+    next player), game_ended with scores, observe and square_counts, all against the oracle."""
+    eng, o = engines[preset], oracles[preset]
+    N, P = o.N, o.P
+    assert eng.A == o.A and eng.W == o.W
+    bpw = 64 // N
+    boards = sweep_boards[preset]
+    n_ended = sum(o.game_ended(s) is not None for s in boards)
+    assert 0 < n_ended < len(boards)  # finished and running games both occur
+    rng = np.random.default_rng(N * 10 + P)
+    for B in sorted({1, bpw - 1, bpw, bpw + 1, 5 * bpw + 2} - {0}):
+        st_h = np.ascontiguousarray(boards[(B + np.arange(B)) % len(boards)])
+        st = torch.from_numpy(st_h).to(eng.device)
+        ref_masks, ref_counts = o.legal_mask_batch(st_h)
+        masks = torch.full((B + 1, eng.W), -1, dtype=torch.int64, device=eng.device)
+        counts = torch.full((B + 1,), -7, dtype=torch.int32, device=eng.device)
+        eng.legal_mask_into(st, masks[:B], counts[:B])
+        assert (_np(counts[:B]) == ref_counts).all(), B
+        assert (_np(masks[:B]).view(np.uint64) == ref_masks).all(), B
+        assert int(counts[B]) == -7 and bool((masks[B] == -1).all())
+        for shift in range(P):
+            pl = [(b + shift) % P for b in range(B)]
+            masks.fill_(-1)
+            counts.fill_(-7)
+            eng.legal_mask_into(st, masks[:B], counts[:B], torch.tensor(pl, dtype=torch.int32, device=eng.device))
+            m_h, c_h = _np(masks[:B]).view(np.uint64), _np(counts[:B])
+            for b in range(B):
+                ref_m, ref_n = o.legal_mask(st_h[b], pl[b])
+                assert c_h[b] == ref_n and (m_h[b] == ref_m).all(), (B, shift, b)
+            assert int(counts[B]) == -7 and bool((masks[B] == -1).all())
+
+        ids, cnt = eng.legal_ids(st, cap=2048)
+        ids_h, cnt_h = _np(ids), _np(cnt)
+        acts = np.full(B, -1, dtype=np.int32)
+        for b in range(B):
+            ref_ids = np.nonzero(np.unpackbits(ref_masks[b].view(np.uint8), bitorder="little")[: o.A])[0]
+            assert cnt_h[b] == len(ref_ids) and (ids_h[b, :len(ref_ids)] == ref_ids).all(), (B, b)
+            if len(ref_ids):
+                acts[b] = int(ref_ids[int(rng.integers(len(ref_ids)))])
+        out, nxt, status = eng.next_state(st, torch.from_numpy(acts).to(eng.device))
+        out_h, nxt_h = _np(out), _np(nxt)
+        assert (_np(status) == 0).all()
+        ended, scores = eng.game_ended(st)
+        ended_h, scores_h = _np(ended), _np(scores)
+        obs_h, sq_h = _np(eng.observe(st)), _np(eng.square_counts(st))
+        for b in range(B):
+            ref_next = o.next_state(st_h[b], int(acts[b]))[0] if acts[b] >= 0 else st_h[b]
+            assert (out_h[b] == ref_next).all(), (B, b)
+            assert int(out_h[b, 336:344].view(np.uint64)[0]) == o.hash(ref_next)
+            assert nxt_h[b] == Oracle.to_move(ref_next)
+            ref_scores = o.game_ended(st_h[b])
+            assert bool(ended_h[b]) == (ref_scores is not None) == (acts[b] < 0), (B, b)
+            if ref_scores is not None:
+                assert (scores_h[b] == ref_scores).all(), (B, b)
+            assert (obs_h[b] == o.observe(st_h[b])).all(), (B, b)
+            assert (sq_h[b] == o.square_counts(st_h[b])).all(), (B, b)
+
+
+# (preset, seed0, max_plies) as the leaf-net, search and self-play tests of these presets draw them
+RANDOM_BOARDS = [((14, 4, 5), 11, 12), ((14, 4, 5), 5, 63), ((14, 2, 5), 9, 12), ((14, 2, 5), 5, 31),
+                 ((20, 2, 5), 9, 12), ((20, 2, 5), 11, 24)]
+
+
+@pytest.mark.parametrize("preset,seed0,max_plies", RANDOM_BOARDS)
+def test_random_boards_match_oracle_recipe(engines, oracles, preset, seed0, max_plies):
+    """boards.random_boards, which the tests of the newer presets draw their states from, equals
+    Oracle.random_board byte for byte (first 16 boards)."""
     from blokus_rl_amd.boards import random_boards
-    st = _np(random_boards(eng, 32, seed0=3))
-    for b in range(32):
-        assert int(st[b, 336:344].view(np.uint64)[0]) == o.hash(st[b])
+    eng, o = engines[preset], oracles[preset]
+    st_h = _np(random_boards(eng, 16, seed0=seed0, max_plies=max_plies))
+    for b in range(16):
+        assert (st_h[b] == o.random_board(seed0 + b, max_plies)).all(), b
+
+
+def test_hash_is_board_only(engines, oracles):
+    from blokus_rl_amd.boards import random_boards
+    for preset in ((20, 4, 5), (14, 4, 5), (14, 2, 5), (20, 2, 5)):
+        eng, o = engines[preset], oracles[preset]
+        st = _np(random_boards(eng, 32, seed0=3))
+        for b in range(32):
+            assert int(st[b, 336:344].view(np.uint64)[0]) == o.hash(st[b]), (preset, b)
 
 
 @pytest.mark.parametrize("wpb", ["2", "4", "8", "11", "14", "21", "31", "40", "45", "46", "items"])
@@ -185,14 +296,17 @@ def test_legal_kernel_variants_bit_exact(oracles, monkeypatch, wpb):
     wave; 31 = the staged kernel without LDS atomics; 40 = round 4's default step on bit-reversed
     rows; 45 / 46 = the lean step on 3 / 2 waves per group; the default, the lean step on one wave,
     is every other test's) and the item-loop kernel give the oracle's masks on the config-2 boards
-    and on 7x7 mid-game boards."""
+    and on 7x7 mid-game boards, and on 14x14, 2-player 20x20 and 9-piece 20x20 boards: (20, 4, 4)
+    under BK_LEGAL_WPB=31 is the staged kernel with 9 pieces, a prefix of the pack table's 21, and
+    (20, 2, 5) is the compile-time 20x20 path with two empty colour planes."""
     from blokus_rl_amd.boards import random_boards
     from blokus_rl_amd.engine import Engine
     if wpb == "items":
         monkeypatch.setenv("BK_LEGAL_KERNEL", "items")
     else:
         monkeypatch.setenv("BK_LEGAL_WPB", wpb)
-    for preset, B in (((20, 4, 5), 1024), ((7, 2, 5), 257), ((7, 2, 4), 100)):
+    for preset, B in (((20, 4, 5), 1024), ((7, 2, 5), 257), ((7, 2, 4), 100),
+                      ((14, 4, 5), 130), ((20, 2, 5), 100), ((20, 4, 4), 100)):
         eng, o = Engine(*preset), oracles[preset]
         st = random_boards(eng, B, seed0=5)
         masks, counts = eng.legal_mask(st)

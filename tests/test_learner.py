@@ -180,19 +180,23 @@ def test_hip_policy_loss_matches_reference(tag):
 
 
 @pytest.mark.gpu
-def test_replay_batch_decodes_rows():
-    """bk_replay_batch == bk_observe(states) + the packed (ids, pi, k, z), bit for bit."""
+@pytest.mark.parametrize("preset,ids_cap", [((20, 4, 5), 1024), ((14, 2, 5), 1024), ((7, 2, 5), 256)],
+                         ids=["20x4x5", "14x2x5", "7x2x5"])
+def test_replay_batch_decodes_rows(preset, ids_cap):
+    """bk_replay_batch == bk_observe(states) + the packed (ids, pi, k, z), bit for bit, on the
+    boards the learner trains from: z is P wide in a row's four slots."""
     from blokus_rl_amd import replay
     from blokus_rl_amd.boards import random_boards
     from blokus_rl_amd.engine import Engine
 
-    eng = Engine(20, 4, 5)
+    eng = Engine(*preset)
     states = random_boards(eng, 96, seed0=3, max_plies=40)
-    ids, counts = eng.legal_ids(states, cap=1024)
+    ids, counts = eng.legal_ids(states, cap=ids_cap)
+    assert int(counts.min()) >= 0  # no row overflowed the cap
     k = counts.clamp(min=0)
     g = torch.Generator(device="cuda").manual_seed(1)
     pi = torch.rand(ids.shape, device="cuda", generator=g)
-    z = torch.randint(-1, 4, (96, 4), device="cuda").float()
+    z = torch.randint(-1, 4, (96, eng.P), device="cuda").float()
     buf, cap = replay.pack(states, ids, pi, k, z)
     index = torch.tensor([5, 0, 95, 17, 17, 60], device="cuda")
     out = eng.replay_batch(buf, cap, index, with_states=True)

@@ -78,6 +78,49 @@ def test_replay_7x7():
     assert s_draw.tolist() == [1.0, 1.0]
 
 
+BRUTE_PRESETS = [(14, 4, 5), (14, 2, 5), (20, 2, 5), (20, 4, 4), (20, 4, 5),
+                 (5, 2, 5), (8, 4, 5), (13, 4, 5), (16, 4, 5), (7, 2, 5)]
+
+
+@pytest.mark.parametrize("preset", BRUTE_PRESETS, ids=lambda p: "x".join(map(str, p)))
+def test_oracle_matches_brute_force(preset):
+    """The recordings pin the oracle at 20x20 and 7x7 only; at every preset the GPU tests use it as
+    the reference, 4 random games against rules_brute.BruteRules: every colour's legal ids at every
+    ply, the next mover under the skip rule, the end of the game, the final square counts and
+    scores."""
+    from rules_brute import BruteRules
+
+    o = Oracle(*preset)
+    P = o.P
+    cells, piece_of = o.action_cells(), o.action_table()[:, 0]
+    for seed in range(4):
+        rng = np.random.default_rng(7000 + seed)
+        br = BruteRules(o.N, P, cells, piece_of)
+        s = o.init_state()
+        prev = None  # the colour that moved last
+        for ply in range(P * o.num_pieces + 1):
+            bf = [br.legal_ids(q) for q in range(P)]
+            for q in range(P):
+                assert o.legal_ids(s, q).tolist() == bf[q].tolist(), (seed, ply, q)
+            movers = [q for q in range(P) if len(bf[q])]
+            ended = o.game_ended(s)
+            assert (ended is not None) == (not movers), (seed, ply)
+            if not movers:
+                break
+            mover = Oracle.to_move(s)
+            first = 0 if prev is None else next((prev + d) % P for d in range(1, P + 1) if len(bf[(prev + d) % P]))
+            assert mover == first, (seed, ply)
+            a = int(bf[mover][int(rng.integers(len(bf[mover])))])
+            s, nxt = o.next_state(s, a)
+            assert nxt == Oracle.to_move(s)
+            br.play(mover, a)
+            prev = mover
+        else:
+            pytest.fail("game did not end")
+        assert o.square_counts(s).tolist() == br.square_counts().tolist(), seed
+        assert ended.tolist() == br.scores().tolist(), seed
+
+
 def test_next_state_is_functional(oracle20):
     st = oracle20.init_state()
     before = st.copy()
