@@ -3,7 +3,8 @@
 Rollouts never leave the GPU: BlokusVectorEnv steps all envs in one kernel and hands back the
 agent's legal-move bitmask; the rollout's draw (FilterLegalMoves + Categorical sample + log_prob of
 get_action_and_value, ppo/agent.py:27-42, 148-156) is one kernel over the actor's raw logits and
-that bitmask (bk_vec_policy; `device_sampling=False` keeps the torch Categorical path); GAE is one kernel over
+that bitmask (bk_vec_policy) on the 7x7 presets that have it; every other board, and
+`device_sampling=False`, takes the torch Categorical path over bk_filter_legal; GAE is one kernel over
 the [T, E] rollout (bk_ppo_gae, the reference's float32 operation order). The update
 (`optimize_agent`) is the reference's clipped-surrogate PPO step — same minibatch order (it
 draws its shuffles from np.random exactly as the reference does, so a seeded run matches),
@@ -158,12 +159,19 @@ def optimize_agent(agent: nn.Module, optimizer, batch: dict, hp) -> dict:
 
 
 class PPOTrainer:
-    """PPOTrainer (trainer.py:20-400) with the device vector env instead of SyncVectorEnv."""
+    """PPOTrainer (trainer.py:20-400) with the device vector env instead of SyncVectorEnv, on any
+    2-player preset the env takes. The rollout's draw is fused into the env step where the preset
+    has that kernel (7x7, max_piece_cells 4 or 5) and is torch's Categorical elsewhere; see
+    `device_sampling`."""
 
-    def __init__(self, hparams: PPOHparams, device: str | torch.device | None = None, device_sampling: bool = True,
-                 channels_last: bool = False, phase_timers: bool = False, device_convs: bool | None = None):
-        """device_sampling: the rollout's draw in one kernel (bk_vec_policy) instead of torch's
-        Categorical; channels_last: the cnn agent's convolutions in NHWC (off by default: measured
+    def __init__(self, hparams: PPOHparams, device: str | torch.device | None = None,
+                 device_sampling: bool | None = None, channels_last: bool = False, phase_timers: bool = False,
+                 device_convs: bool | None = None):
+        """device_sampling: the rollout's draw inside the env step (bk_vec_step_policy) instead of
+        torch's Categorical over FilterLegalMoves; None (the default) takes it where the env's
+        preset has the kernels (`envs.policy_kernels`: 7x7 with max_piece_cells 4 or 5) and the
+        torch path on every other board; True on a preset without them is a ValueError here;
+        channels_last: the cnn agent's convolutions in NHWC (off by default: measured
         round 6, MIOPEN_FIND_MODE=FAST, 8192 envs, 23.1 s per update against 2.0 s in NCHW — MIOpen
         then picks composable-kernel grouped convolutions instead of its NCHW implicit GEMMs;
         parameters and checkpoint keys are the same either way); phase_timers: synchronize and accumulate rollout / update seconds in
@@ -172,10 +180,12 @@ class PPOTrainer:
         throughout) where the agent qualifies (7x7 boards, d_model 128; any other agent keeps
         PyTorch's path); None reads BK_PPO_CONV from the environment (x3 = on), off by default."""
         self.hparams = hp = hparams
-        self.device_sampling = device_sampling
         self.phase_timers = phase_timers
         self.phase_s = {"rollout": 0.0, "gae": 0.0, "update": 0.0}
         self.envs = BlokusVectorEnv(hp.num_envs, hp.board_size, hp.max_piece_cells, device=device)
+        if device_sampling:
+            self.envs.require_policy_kernels("PPOTrainer(device_sampling=True)")
+        self.device_sampling = self.envs.policy_kernels if device_sampling is None else bool(device_sampling)
         self.device = self.envs.device
         self.obs_shape = (hp.board_size, hp.board_size)
         self.agent = get_agent(hp.agent_type)(self.obs_shape, self.envs.single_action_space_n, hp).to(self.device)

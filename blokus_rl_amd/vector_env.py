@@ -25,6 +25,9 @@ class BlokusVectorEnv:
         dev = self.eng.device
         self.device = dev
         self.single_action_space_n = self.eng.A
+        # the masked-policy draw (bk_vec_policy / bk_vec_step_policy) exists for the 7x7 presets
+        # with 9 or 21 pieces (max_piece_cells 4 or 5) only
+        self.policy_kernels = self.eng.N == 7 and self.eng.num_pieces in (9, 21)
         self.states = torch.empty((E, 384), dtype=torch.uint8, device=dev)
         self.rng = torch.zeros(E, dtype=torch.int64, device=dev)
         self.obs = torch.empty((E, board_size, board_size), dtype=torch.uint8, device=dev)
@@ -66,13 +69,20 @@ class BlokusVectorEnv:
                                         _ptr(self.obs), _ptr(self.mask_words), _ptr(self.reward), _ptr(self.done),
                                         self._s()))
 
+    def require_policy_kernels(self, what: str):
+        if not self.policy_kernels:
+            raise ValueError(f"{what}: the device policy draw exists for the 7x7 presets with max_piece_cells 4 or 5 "
+                             f"only, not for board_size={self.eng.N}, max_piece_cells={self.eng.max_cells}")
+
     def sample_policy(self, logits: torch.Tensor, zero_masked: bool = True):
         """The agent's moves drawn from its policy on the device (bk_vec_policy): the rollout's
         `get_action_and_value(obs, possible_moves=...)` sample + log_prob (ppo/agent.py:148-156)
         over FilterLegalMoves (:27-42; zero_masked = its rule that a legal logit of exactly 0 is
         masked too) in one launch, from the actor's raw logits [E, A] f32 and the env's current
         legal-move bitmask. Returns (actions [E] int32, logp [E] f32), updated in place
-        (capturable in a HIP graph: the checks are host-side)."""
+        (capturable in a HIP graph: the checks are host-side). ValueError on a preset without
+        the kernel (`policy_kernels` False)."""
+        self.require_policy_kernels("sample_policy")
         E, A = self.num_envs, self.eng.A
         if not (logits.is_cuda and logits.device == torch.device(self.device) and logits.dtype == torch.float32
                 and logits.is_contiguous() and tuple(logits.shape) == (E, A)):
@@ -86,7 +96,8 @@ class BlokusVectorEnv:
         (bk_vec_step_policy: the draw reads the agent's legal mask from the step's own legality
         pass); fused=False: sample_policy then step_raw (two launches, the same results bit for
         bit). Returns (actions, logp) of the step; obs / mask_words / reward / done in place.
-        Capturable in a HIP graph."""
+        Capturable in a HIP graph. ValueError on a preset without the kernels."""
+        self.require_policy_kernels("step_policy")
         if not fused:
             self.sample_policy(logits, zero_masked)
             self.step_raw(self.actions)

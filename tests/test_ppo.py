@@ -132,6 +132,84 @@ def test_filter_kernel_matches_reference():
     assert torch.equal(out, out2)
 
 
+def _filter_case(E, A, seed):
+    """Masks of density ~0.02 with, from three rows up, an all-zero first and an all-ones last row;
+    logits normal x 3 with exact +0.0 and -0.0 planted on legal and on illegal ids of every row
+    that has both kinds (the reference masks a legal exact zero, and -0.0 == 0)."""
+    rng = np.random.default_rng(seed)
+    m = (rng.random((E, A)) < 0.02).astype(np.uint8)
+    m[:, (0, 1, A - 2, A - 1)] = 1  # the first ids and the last (the last mask word's top used bits)
+    if E >= 3:
+        m[0], m[-1] = 0, 1
+    x = (rng.standard_normal((E, A)) * 3.0).astype(np.float32)
+    z = rng.random((E, A))
+    x[z < 0.03] = 0.0
+    x[(z >= 0.03) & (z < 0.06)] = -0.0
+    for e in range(E):
+        for ids in (np.flatnonzero(m[e]), np.flatnonzero(m[e] == 0)):
+            if ids.size >= 4:
+                x[e, ids[[0, -1]]] = (1.5, -2.5)
+                x[e, ids[[1, -2]]] = (0.0, -0.0)
+    return x, m
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("E,A", [(5, 387), (3, 13729), (1, 49), (140, 30433)])
+def test_filter_kernel_other_shapes_match_oracle(E, A):
+    """bk_filter_legal against oracle.ppo_oracle.filter_legal (a copy or a constant: exact) at
+    the 2-player presets' action counts: masks of 7, 215, 1 and 476 words, each with a partly
+    used last word, and 140 x 30433 = 4.26 M elements, past the 16384 x 256 grid, so the
+    grid-stride loop takes a second trip. Mask bits at positions >= A must change nothing."""
+    from blokus_rl_amd.ppo.agent import FilterLegalMoves, ids_to_mask_words
+
+    assert (E * A > 16384 * 256) == (E == 140)
+    x_h, m = _filter_case(E, A, seed=A)
+    zero = x_h == 0
+    neg = np.signbit(x_h)
+    for legal in (m == 1, m == 0):  # the planted cases are there
+        assert (zero & neg & legal).any() and (zero & ~neg & legal).any() and (~zero & legal).any()
+    want = filter_legal(x_h, m)
+    x = torch.from_numpy(x_h).cuda()
+    ids = [np.flatnonzero(r) for r in m]
+    out = FilterLegalMoves()(x, ids)
+    assert np.array_equal(out.cpu().numpy(), want)
+    words = ids_to_mask_words(ids, A, "cuda")
+    assert tuple(words.shape) == (E, (A + 63) // 64) and A % 64 != 0
+    assert torch.equal(FilterLegalMoves()(x, words), out)
+    stray = words.clone()
+    stray[:, -1] |= -1 << (A % 64)  # every bit of the last word from position A up
+    assert not torch.equal(stray, words)
+    assert torch.equal(FilterLegalMoves()(x, stray), out)
+    assert np.array_equal(x.cpu().numpy().view(np.uint32), x_h.view(np.uint32))  # the input is left alone
+
+
+@pytest.mark.gpu
+def test_filter_autograd_routes_gradient_through_kept_logits():
+    """FilterLegalMoves with a logits tensor that wants a gradient: the forward values are the
+    kernel's, and the gradient is the reference op's (y = x * mask; y[y == 0] = -1e9, restated in
+    float64 torch): g where the output kept x, exactly 0 elsewhere (illegal ids and legal zeros)."""
+    from blokus_rl_amd.ppo.agent import FilterLegalMoves, ids_to_mask_words
+
+    E, A = 5, 387
+    x_h, m = _filter_case(E, A, seed=1)
+    words = ids_to_mask_words([np.flatnonzero(r) for r in m], A, "cuda")
+    x = torch.from_numpy(x_h).cuda().requires_grad_()
+    y = FilterLegalMoves()(x, words)
+    assert y.requires_grad and np.array_equal(y.detach().cpu().numpy(), filter_legal(x_h, m))
+    g = torch.from_numpy(np.random.default_rng(2).standard_normal((E, A)).astype(np.float32)).cuda()
+    y.backward(g)
+    x64 = torch.from_numpy(x_h).double().requires_grad_()
+    y64 = x64 * torch.from_numpy(m).double()
+    y64 = y64.masked_fill(y64 == 0, -1e9)
+    y64.backward(g.cpu().double())
+    assert torch.equal(x.grad.cpu().double(), x64.grad)
+    keep = y.detach() != -1e9
+    assert 0 < int(keep.sum()) < int(torch.from_numpy(m).sum())  # some legal logits were zeros
+    assert torch.equal(x.grad, torch.where(keep, g, torch.zeros_like(g)))
+    with torch.no_grad():  # and without a graph the kernel's output comes back as it is
+        assert not FilterLegalMoves()(x, words).requires_grad
+
+
 @pytest.mark.gpu
 def test_agent_masked_outputs_match_reference_gpu():
     agent = _agent("cuda")
@@ -176,17 +254,25 @@ def test_ppo_trainer_updates_on_device_env(tmp_path):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("device_sampling", [True, False])
-def test_ppo_rollout_draws(device_sampling):
+@pytest.mark.parametrize("board_size,max_cells,device_sampling", [
+    pytest.param(7, 4, True, id="True"), pytest.param(7, 4, False, id="False"),
+    pytest.param(5, 5, None, id="5x5-5-default"), pytest.param(7, 3, None, id="7x7-3-default")])
+def test_ppo_rollout_draws(board_size, max_cells, device_sampling):
     """The rollout's draw on the device (bk_vec_policy over the actor's raw logits) or through torch's
-    Categorical over FilterLegalMoves: the stored actions are the drawn ones and their log-probs are
-    finite and <= 0; a device draw is a legal id unless every legal logit of its row is exactly 0 —
-    the reference filter's all -1e9 row (ppo/agent.py:40-41), uniform over every id, which the
-    freshly initialised agent produces for a few envs whose last hidden layer is all zero."""
+    Categorical over FilterLegalMoves (the trainer's own default on the presets without the draw
+    kernels): the stored actions are the drawn ones and their log-probs are finite and <= 0; a
+    draw is a legal id unless every legal logit of its row is exactly 0 — the reference filter's
+    all -1e9 row (ppo/agent.py:40-41), uniform over every id, which the freshly initialised agent
+    produces for a few envs whose last hidden layer is all zero. That holds for torch's draw over
+    the filter as well: a masked id has probability exp(-1e9 - max) = 0 in float32."""
     from blokus_rl_amd.ppo.trainer import PPOTrainer
 
-    hp = _hp(num_envs=64, num_steps=16, total_timesteps=64 * 16, agent_type="cnn", save_interval=10**6)
-    tr = PPOTrainer(hp, device_sampling=device_sampling)
+    hp = _hp(num_envs=64, num_steps=16, total_timesteps=64 * 16, agent_type="cnn", save_interval=10**6,
+             board_size=board_size, max_piece_cells=max_cells)
+    tr = PPOTrainer(hp) if device_sampling is None else PPOTrainer(hp, device_sampling=device_sampling)
+    assert tr.device_sampling is (tr.envs.policy_kernels if device_sampling is None else device_sampling)
+    assert tr.envs.policy_kernels is ((board_size, max_cells) == (7, 4))
+    device_sampling = tr.device_sampling
     obs, _ = tr.envs.reset(seed=0)
     masks, acts, rows = [], [], []
     orig_step, orig_sample = tr.envs.step, tr.envs.sample_policy
@@ -210,16 +296,18 @@ def test_ppo_rollout_draws(device_sampling):
         return a, lp
 
     tr.envs.step, tr.envs.sample_policy, tr.envs.step_policy = rec_step, rec_sample, rec_step_policy
+    if not device_sampling:  # the torch path: the actor's raw logits are the filter's input
+        tr.agent.actor.filter_legal_moves.register_forward_hook(lambda mod, args, out: rows.append(args[0].clone()))
     tr._play_env(obs.float(), torch.zeros(64, device=tr.device))
-    assert len(acts) == hp.num_steps
+    assert len(acts) == hp.num_steps and len(rows) == hp.num_steps
     illegal = 0
     for t, (m, a) in enumerate(zip(masks, acts)):
         assert torch.equal(tr.memory.actions[t].long(), a)
         bad = ~m.gather(1, a.view(-1, 1)).view(-1)
-        if device_sampling:
-            no_candidate = ~(m & (rows[t] != 0)).any(dim=1)
-            assert bool((no_candidate | ~bad).all()), (t, torch.nonzero(bad & ~no_candidate).view(-1).tolist())
+        no_candidate = ~(m & (rows[t] != 0)).any(dim=1)
+        assert bool((no_candidate | ~bad).all()), (t, torch.nonzero(bad & ~no_candidate).view(-1).tolist())
         illegal += int(bad.sum())
     lp = tr.memory.logprobs
     assert bool(torch.isfinite(lp).all()) and bool((lp <= 0).all())
-    assert device_sampling or illegal <= 64  # torch's draw over the same filter (same quirk)
+    if (board_size, max_cells) == (7, 4):
+        assert device_sampling or illegal <= 64  # torch's draw over the same filter (same quirk)

@@ -430,17 +430,28 @@ def test_trainer_runs_on_the_device_convs(tmp_path, monkeypatch):
     assert type(PPOTrainer(_hp(tmp_path), device_convs=None).agent.conv_block) is not DeviceConvBlock
 
 
-@pytest.mark.parametrize("kw", [dict(d_model=64), dict(board_size=5)])
+@pytest.mark.parametrize("kw", [dict(d_model=64), dict(board_size=5), dict(board_size=5, max_piece_cells=5)])
 def test_trainer_falls_back_for_unsupported_agents(tmp_path, monkeypatch, kw):
     """(the rollout's fused draw + step kernel is the 7x7 presets': a 5x5 board takes the trainer's
-    torch Categorical path, device_sampling=False)"""
+    torch Categorical path by the trainer's own default)"""
     import math
 
     from blokus_rl_amd.ppo.agent import CnnAgent, ConvBlock
     from blokus_rl_amd.ppo.trainer import PPOTrainer
 
     monkeypatch.delenv("BK_PPO_CONV", raising=False)
-    tr = PPOTrainer(_hp(tmp_path, **kw), device_convs=True, device_sampling=kw.get("board_size", 7) == 7)
+    tr = PPOTrainer(_hp(tmp_path, **kw), device_convs=True)
+    assert tr.device_sampling is (kw.get("board_size", 7) == 7)
     assert not tr.device_convs and type(tr.agent) is CnnAgent and type(tr.agent.conv_block) is ConvBlock
     logs = tr.train(2)
     assert len(logs) == 2 and math.isfinite(float(logs[-1]["loss"]))
+
+
+def test_trainer_refuses_device_sampling_without_the_kernels(tmp_path):
+    from blokus_rl_amd.ppo.trainer import PPOTrainer
+
+    with pytest.raises(ValueError, match="board_size=5, max_piece_cells=4"):
+        PPOTrainer(_hp(tmp_path, board_size=5), device_sampling=True)
+    assert PPOTrainer(_hp(tmp_path, board_size=5), device_sampling=False).device_sampling is False
+    assert PPOTrainer(_hp(tmp_path), device_sampling=False).device_sampling is False
+    assert PPOTrainer(_hp(tmp_path)).device_sampling is True

@@ -3,7 +3,8 @@ states, observations, masks, rewards, dones and the per-env random streams bit-e
 steps and episodes — agent actions given (random legal ids chosen on the host, plus out-of-range
 and illegal ids, which end the episode as a loss) and drawn in-kernel; a partial last workgroup
 (E not a multiple of the envs per workgroup), both lane widths of k_vec_step7 and the
-one-wave-per-env kernel; and the benchmark size (8192 envs, and 8190) driven through a captured
+one-wave-per-env kernel, that one also on the presets that only it serves (5x5 to 20x20), stepped
+and inside a captured graph; and the benchmark size (8192 envs, and 8190) driven through a captured
 HIP graph of back-to-back step_raw launches as bench.py replays it (ppo/trainer.py:128-175)."""
 import numpy as np
 import pytest
@@ -27,8 +28,10 @@ def _assert_env_equal(env, ref, tag):
     want = np.stack(ref.states)
     bad = np.nonzero((st != want).any(axis=1))[0]
     assert bad.size == 0, (tag, "state", bad[:8])
-    assert (env.obs.cpu().numpy() == _obs_of(want)).all(), (tag, "obs")
+    obs = env.obs.cpu().numpy()
+    assert obs.shape == (E, ref.o.N, ref.o.N) and (obs == _obs_of(want, ref.o.N)).all(), (tag, "obs")
     m = env.mask_words.cpu().numpy().view(np.uint64)
+    assert m.shape == (E, ref.o.W), (tag, "mask", m.shape)
     for e in range(E):
         assert (m[e] == ref.mask(e)).all(), (tag, "mask", e)
     assert (env.rng.cpu().numpy().view(np.uint64) == np.array(ref.rng, dtype=np.uint64)).all(), (tag, "rng")
@@ -83,13 +86,110 @@ def test_vector_env_matches_oracle(max_cells, E, kernel, monkeypatch):
     assert episodes > E and losses > 0  # several episodes per env ended and auto-reset
 
 
-def _graph_rollout(E, steps_per_graph, replays, seed):
+def _run_schedule(ref, env, T, period, seed=0):
+    """T vector steps of the three action sources on `ref` and, when given, on `env` beside it
+    (env None: the oracle alone, which is how the schedules below were chosen). Step t with
+    t % period == period - 1 is a forcing step: env e gets kind (e + t // period) % 3 — 0 an id
+    >= A, 1 an id in range that is not legal, 2 a legal id — so the kinds rotate over the envs and
+    every env also plays undisturbed stretches. Other steps: t % 3 == 2 the in-kernel uniform
+    agent (-1), else legal ids chosen here. The actions depend on the oracle's masks only, so
+    the oracle alone walks the same trajectory. -> natural game ends per env, forced losses per
+    kind, the set of rewards at natural ends."""
+    E, A = ref.E, ref.o.A
+    rng = np.random.default_rng(seed)
+    natural = np.zeros(E, dtype=np.int64)
+    forced = [0, 0]
+    rewards = set()
+    for t in range(T):
+        if env is not None:
+            _assert_env_equal(env, ref, t)
+        legal = [np.nonzero(np.unpackbits(ref.mask(e).view(np.uint8), bitorder="little")[:A])[0] for e in range(E)]
+        kind = np.full(E, 2)
+        if t % period == period - 1:
+            kind = (np.arange(E) + t // period) % 3
+            acts = np.empty(E, dtype=np.int32)
+            for e in range(E):
+                if kind[e] == 0:
+                    acts[e] = A + int(rng.integers(0, 4096))
+                elif kind[e] == 1:
+                    acts[e] = int(rng.choice(np.setdiff1d(np.arange(A), legal[e])))
+                else:
+                    acts[e] = int(rng.choice(legal[e]))
+        elif t % 3 == 2:
+            acts = np.full(E, -1, dtype=np.int32)
+        else:
+            acts = np.array([int(rng.choice(legal[e])) for e in range(E)], dtype=np.int32)
+        if env is not None:
+            _, rew, term, _, _ = env.step(torch.from_numpy(acts))
+            rew, term = rew.cpu().numpy(), term.cpu().numpy()
+        for e in range(E):
+            r, d = ref.step(e, int(acts[e]))
+            if env is not None:
+                assert rew[e] == r and bool(term[e]) == bool(d), (t, e, acts[e])
+            if kind[e] != 2:
+                assert r == -1.0 and d == 1, (t, e)
+                forced[kind[e]] += 1
+            elif d:
+                natural[e] += 1
+                rewards.add(r)
+    if env is not None:
+        _assert_env_equal(env, ref, "end")
+    return natural, forced, rewards
+
+
+# (N, cells, E, T, period, seed of the host's choices): the 2-player presets that run on the
+# one-wave-per-env k_vec_step / k_vec_reset by themselves. Big boards need rare forcing steps or
+# nobody ever finishes a game (an undisturbed 14x14 episode takes 12-15 agent steps, a 20x20 one
+# 19-21). 7x7/3 (four pieces, nine squares a side) ends level in ~98% of random games: T and the seed
+# there are the first of a small scan, on the oracle alone, at which a win and a loss both occur.
+# Natural ends per env / forced losses [out of range, illegal] / rewards at natural ends, from
+# the oracle alone:
+GENERIC_PRESETS = [
+    (5, 4, 5, 60, 7, 0),     # [12, 16, 16, 13, 15] / [13, 14] / -1 0 +1
+    (5, 4, 1, 60, 7, 0),     # [15]                 / [3, 3]   / -1 +1
+    (5, 5, 5, 60, 7, 0),     # [16, 18, 18, 17, 20] / [13, 14] / -1 0 +1
+    (7, 1, 5, 60, 7, 0),     # [54, 55, 55, 54, 55] / [13, 14] / 0
+    (7, 3, 5, 90, 7, 6),     # [17, 17, 17, 17, 17] / [20, 20] / -1 0 +1
+    (8, 5, 5, 60, 7, 0),     # [9, 6, 8, 5, 6]      / [13, 14] / -1 0 +1
+    (14, 5, 4, 48, 23, 0),   # [2, 2, 2, 2]         / [3, 3]   / -1 +1
+    (20, 5, 4, 64, 23, 0),   # [2, 3, 2, 2]         / [3, 3]   / -1 0 +1
+]
+
+
+@pytest.mark.parametrize("N,cells,E,T,period,seed", GENERIC_PRESETS)
+def test_generic_vector_env_matches_oracle(N, cells, E, T, period, seed, monkeypatch):
+    """k_vec_step / k_vec_reset on boards other than 7x7/4|5 (no BK_VEC_WAVE: these presets reach
+    them on their own): odd W64 (5x5/4: W32pad != 2 W64), one mask word and an episode per step
+    (7x7/1), a 7x7 that is not k_vec_step7's (7x7/3), a full byte row (8x8), and 7 / 15 passes of
+    kth_legal's 64-lane scan (14x14, 20x20). States, obs, masks, random streams before every step
+    and at the end, rewards and dones every step, bit for bit; and the run is not vacuous."""
+    from blokus_rl_amd.vector_env import BlokusVectorEnv
+
+    monkeypatch.delenv("BK_VEC_WAVE", raising=False)
+    env = BlokusVectorEnv(E, N, cells)
+    ref = VecEnvOracle(E, N, cells)
+    assert env.eng.A == ref.o.A and env.eng.W == ref.o.W and env.policy_kernels is False
+    env.reset(seed=5)
+    ref.reset(seed=5)
+    natural, forced, rewards = _run_schedule(ref, env, T, period, seed)
+    assert (natural >= 2).all(), natural  # every env played at least 2 games to the end
+    assert forced[0] > 0 and forced[1] > 0, forced
+    if cells == 1:
+        # one monomino each: every game is a 1-1 draw, and every agent step ends an episode
+        assert rewards == {0.0} and int(natural.sum()) + sum(forced) == T * E, (rewards, natural, forced)
+    else:
+        assert {1.0, -1.0} <= rewards, rewards
+    if (N, cells) == (7, 3):
+        assert 0.0 in rewards
+
+
+def _graph_rollout(E, steps_per_graph, replays, seed, board_size=7, max_cells=4):
     """The bench's config-5 loop: a HIP graph of `steps_per_graph` in-kernel-agent step_raw
     launches, replayed; the env checked against the oracle after every replay."""
     from blokus_rl_amd.vector_env import BlokusVectorEnv
 
-    env = BlokusVectorEnv(E, 7, 4)
-    ref = VecEnvOracle(E, 7, 4)
+    env = BlokusVectorEnv(E, board_size, max_cells)
+    ref = VecEnvOracle(E, board_size, max_cells)
     env.reset(seed=seed)
     ref.reset(seed=seed)
     g = torch.cuda.CUDAGraph()
@@ -122,6 +222,32 @@ def test_vector_env_ragged_size_graph_matches_oracle():
     """8190 envs: not a multiple of the 16 envs of a k_vec_step7 workgroup (the last one holds
     14); a 5-step graph replayed 4 times, checked after each replay."""
     assert _graph_rollout(8190, 5, 4, seed=9) > 8190
+
+
+def test_generic_vector_env_graph_matches_oracle():
+    """k_vec_step itself (14x14, dynamic LDS) captured: 64 envs, a 5-step graph replayed 4 times,
+    checked after each replay. A 14x14 game of the uniform agent takes 12-15 agent steps, so in
+    20 steps every env finishes one (64 ends on the oracle alone)."""
+    assert _graph_rollout(64, 5, 4, seed=9, board_size=14, max_cells=5) >= 64
+
+
+def test_policy_draw_refused_up_front_without_the_kernels():
+    """sample_policy / step_policy on a preset without the draw kernels: a ValueError that names
+    the preset, before any launch (not the library's error), and nothing touched."""
+    from blokus_rl_amd.vector_env import BlokusVectorEnv
+
+    assert BlokusVectorEnv(2, 7, 4).policy_kernels is True and BlokusVectorEnv(2, 7, 5).policy_kernels is True
+    for N, cells in ((5, 5), (7, 3), (8, 5)):
+        env = BlokusVectorEnv(2, N, cells)
+        assert env.policy_kernels is False
+        env.reset(seed=0)
+        before = [t.clone() for t in (env.states, env.rng, env.mask_words, env.actions, env.logp)]
+        x = torch.zeros(2, env.eng.A, device=env.device)
+        for call in (env.sample_policy, env.step_policy, lambda lg: env.step_policy(lg, fused=False)):
+            with pytest.raises(ValueError, match=f"board_size={N}, max_piece_cells={cells}"):
+                call(x)
+        after = (env.states, env.rng, env.mask_words, env.actions, env.logp)
+        assert all(torch.equal(a, b) for a, b in zip(before, after))
 
 
 def test_step_raw_rejects_bad_action_tensors():
