@@ -66,7 +66,14 @@ constexpr int kLnRowWords = kLnP * kMaxN;   // a state's board rows: plane p, ro
 // bk_observe(states) as float values. A board whose status is not 1 (no leaf for the net: its
 // state row is stale) is the all-zero observation, as the search writes it in the planar form;
 // its state words are not loaded.
-template <int N, typename In>  // In: const float* (planes), LnStates or LnRows
+//
+// EDGE (N = 20, the default: BK_LN_EDGE): the pixels sit in MFMA columns by LnEdgePixMap, whose
+// last four groups are pieces of the four board edges, and the tower's chunk loop follows
+// LnEdgeSched: each of those groups leaves out the 6 of 18 chunks whose tap reads only the zero
+// halo (24 of a conv's 450 (group, chunk) pairs, 72 of 1350 MFMAs per wave with their 48
+// ds_read_b128). The products left out are a*0: every output is bitwise the full schedule's
+// (leafnet_common.h ln_chunk_il_act). The stem (4 taps per chunk: nothing to skip) only takes the map.
+template <int N, typename In, bool EDGE_A = false>  // In: const float* (planes), LnStates or LnRows
 __global__ __launch_bounds__(kLnThreads, 1) void k_leafnet_x3(In in,
                                                               const h16x8* __restrict__ wstem_a,
                                                               const float* __restrict__ sstem_a,
@@ -81,6 +88,7 @@ __global__ __launch_bounds__(kLnThreads, 1) void k_leafnet_x3(In in,
   // table in `in`. The other forms take the arguments as they are.
   constexpr bool ROWS = std::is_same<In, LnRows>::value;
   constexpr bool STATES = std::is_same<In, LnStates>::value || ROWS;
+  constexpr bool EDGE = EDGE_A && kLnInterleave;  // a BK_LN_IL=0 build keeps the old map and loop
   const h16x8* __restrict__ wstem = wstem_a;
   const float* __restrict__ sstem = sstem_a;
   const float* __restrict__ bstem = bstem_a;
@@ -174,7 +182,11 @@ __global__ __launch_bounds__(kLnThreads, 1) void k_leafnet_x3(In in,
   unsigned valid = 0;
 #pragma unroll
   for (int g = 0; g < NG; ++g) {
-    const int sl = kLnPixMap<N>.slot[16 * g + n];
+    int sl;
+    if constexpr (EDGE)
+      sl = kLnEdgePixMap<N>.slot[16 * g + n];
+    else
+      sl = kLnPixMap<N>.slot[16 * g + n];
     ab[g] = (sl >= 0 ? sl : RS + 1) * 16 + ks * 4 * PL - kBias;
     valid |= (sl >= 0 ? 1u : 0u) << g;
   }
@@ -433,32 +445,51 @@ __global__ __launch_bounds__(kLnThreads, 1) void k_leafnet_x3(In in,
     };
     ln_prime<NG, PL>(rb, act, ab, coff_of(0));
     if (layer == 1) LNSTAMP(26, __builtin_amdgcn_s_memtime());
+    if constexpr (EDGE) {
+      // the chunk index as a compile-time value: each chunk takes its own list of active groups
+      // (the weight ring as in the loop below)
+      ln_each_chunk(
+          [&](auto cc) __attribute__((always_inline)) {
+            constexpr int c = decltype(cc)::value, cn = c + kLnWpf, sn = cn % (kLnWpf + 1);
+            using S = LnEdgeSched<N>;
+            if (layer == 1 && c == 1) LNSTAMP(27, __builtin_amdgcn_s_memtime());
+            if (layer == 1 && c == 9) LNSTAMP(28, __builtin_amdgcn_s_memtime());
+            const int wl = cn < 18 || more ? layer + cn / 18 : layer;
+            wq[sn][0] = wload(wl, cn % 18, 0);
+            wq[sn][1] = wload(wl, cn % 18, 1);
+            const h16x8* w = wq[c % (kLnWpf + 1)];
+            ln_chunk_il_act<NG, S::active(c), S::first(c), S::pos0(c), PL>(acc, w[0], w[1], act, ab, coff_of(c),
+                                                                         coff_of(c + 1 < 18 ? c + 1 : c), rb);
+          },
+          std::make_integer_sequence<int, 18>{});
+    } else {
 #pragma unroll
-    for (int c = 0; c < 18; ++c) {
-      if (layer == 1 && c == 1) LNSTAMP(27, __builtin_amdgcn_s_memtime());
-      if (layer == 1 && c == 9) LNSTAMP(28, __builtin_amdgcn_s_memtime());
-      const int cn = c + kLnWpf, sn = cn % (kLnWpf + 1);
-      if (cn < 18) {
-        wq[sn][0] = wload(layer, cn, 0);
-        wq[sn][1] = wload(layer, cn, 1);
-      } else {  // the next layer's first chunks; the last layer reloads its own (never used): an
-                // unconditional load keeps the wait count static (a branch made it vmcnt(0), an
-                // exposed L2 round trip per layer)
-        const int nl = more ? layer + 1 : layer;
-        wq[sn][0] = wload(nl, cn - 18, 0);
-        wq[sn][1] = wload(nl, cn - 18, 1);
-      }
-      const h16x8* w = wq[c % (kLnWpf + 1)];
-      if constexpr (kLnInterleave) {
-        if (c == 0)
-          ln_chunk_il<NG, true, PL>(acc, w[0], w[1], act, ab, coff_of(0), coff_of(1), rb);
-        else
-          ln_chunk_il<NG, false, PL>(acc, w[0], w[1], act, ab, coff_of(c), coff_of(c + 1 < 18 ? c + 1 : c), rb);
-      } else {
-        if (c == 0)
-          ln_chunk<NG, true, PL>(acc, w[0], w[1], act, ab, coff_of(0), coff_of(1), rb);
-        else
-          ln_chunk<NG, false, PL>(acc, w[0], w[1], act, ab, coff_of(c), coff_of(c + 1 < 18 ? c + 1 : c), rb);
+      for (int c = 0; c < 18; ++c) {
+        if (layer == 1 && c == 1) LNSTAMP(27, __builtin_amdgcn_s_memtime());
+        if (layer == 1 && c == 9) LNSTAMP(28, __builtin_amdgcn_s_memtime());
+        const int cn = c + kLnWpf, sn = cn % (kLnWpf + 1);
+        if (cn < 18) {
+          wq[sn][0] = wload(layer, cn, 0);
+          wq[sn][1] = wload(layer, cn, 1);
+        } else {  // the next layer's first chunks; the last layer reloads its own (never used): an
+                  // unconditional load keeps the wait count static (a branch made it vmcnt(0), an
+                  // exposed L2 round trip per layer)
+          const int nl = more ? layer + 1 : layer;
+          wq[sn][0] = wload(nl, cn - 18, 0);
+          wq[sn][1] = wload(nl, cn - 18, 1);
+        }
+        const h16x8* w = wq[c % (kLnWpf + 1)];
+        if constexpr (kLnInterleave) {
+          if (c == 0)
+            ln_chunk_il<NG, true, PL>(acc, w[0], w[1], act, ab, coff_of(0), coff_of(1), rb);
+          else
+            ln_chunk_il<NG, false, PL>(acc, w[0], w[1], act, ab, coff_of(c), coff_of(c + 1 < 18 ? c + 1 : c), rb);
+        } else {
+          if (c == 0)
+            ln_chunk<NG, true, PL>(acc, w[0], w[1], act, ab, coff_of(0), coff_of(1), rb);
+          else
+            ln_chunk<NG, false, PL>(acc, w[0], w[1], act, ab, coff_of(c), coff_of(c + 1 < 18 ? c + 1 : c), rb);
+        }
       }
     }
     // the last chunk's read-ahead (ln_chunk_il: untracked) lands before its registers are reused
@@ -611,6 +642,16 @@ __global__ __launch_bounds__(kLnThreads, 1) void k_leafnet_x3(In in,
 }
 
 static_assert(ln_lds_bytes(20) <= 160 * 1024, "k_leafnet_x3<20>: LDS");
+static_assert(ln_edge_map_is_bijection<20>(), "LnEdgePixMap<20>: every board pixel in exactly one MFMA column");
+static_assert(ln_edge_sched_skips_only_halo<20>(), "LnEdgeSched<20>: a skipped (group, chunk) reads only the halo");
+static_assert(LnEdgeSched<20>::pos0(18) == 18 * 25 - 24, "LnEdgeSched<20>: 24 of 450 pairs left out");
+
+// BK_LN_EDGE (default 1): the 20x20 board on the edge schedule (0: the full schedule on
+// LnPixMap); read per launch, so one build compares the two (a captured graph keeps what it read)
+bool ln_edge() {
+  const char* e = getenv("BK_LN_EDGE");
+  return e ? atoi(e) != 0 : true;
+}
 
 }  // namespace
 }  // namespace bk
@@ -651,14 +692,18 @@ int bk_leafnet_x3(const float* obs, int B, int N, int cin, const void* wstem, co
              "bk_leafnet_x3: 16-byte aligned buffers");
   if (B == 0) return BK_OK;
   {
-    const void* fns[2] = {(const void*)k_leafnet_x3<14, const float*>, (const void*)k_leafnet_x3<20, const float*>};
-    if (set_max_dynamic_lds(fns, 2, ln_lds_bytes(20)) != BK_OK) return BK_EHIP;
+    const void* fns[3] = {(const void*)k_leafnet_x3<14, const float*>, (const void*)k_leafnet_x3<20, const float*>,
+                          (const void*)k_leafnet_x3<20, const float*, true>};
+    if (set_max_dynamic_lds(fns, 3, ln_lds_bytes(20)) != BK_OK) return BK_EHIP;
   }
   const LnHeads h{wp, bp, wv, bv, w1t, b1, w2, b2, P, pf, vout};
   hipStream_t s = (hipStream_t)stream;
   const h16x8* ws = reinterpret_cast<const h16x8*>(wstem);
   const h16x8* wt = reinterpret_cast<const h16x8*>(wtower);
-  if (N == 20)
+  if (N == 20 && ln_edge())
+    hipLaunchKernelGGL((k_leafnet_x3<20, const float*, true>), dim3(B), dim3(kLnThreads), ln_lds_bytes(20), s, obs, ws,
+                       sstem, bstem, wt, stower, btower, bounds, nlayers, h, out);
+  else if (N == 20)
     hipLaunchKernelGGL((k_leafnet_x3<20, const float*>), dim3(B), dim3(kLnThreads), ln_lds_bytes(20), s, obs, ws, sstem,
                        bstem, wt, stower, btower, bounds, nlayers, h, out);
   else
@@ -684,15 +729,19 @@ int bk_leafnet_x3_states(const void* states, const int32_t* status, int B, int N
              "bk_leafnet_x3_states: 16-byte aligned buffers");
   if (B == 0) return BK_OK;
   {
-    const void* fns[2] = {(const void*)k_leafnet_x3<14, LnStates>, (const void*)k_leafnet_x3<20, LnStates>};
-    if (set_max_dynamic_lds(fns, 2, ln_lds_bytes(20)) != BK_OK) return BK_EHIP;
+    const void* fns[3] = {(const void*)k_leafnet_x3<14, LnStates>, (const void*)k_leafnet_x3<20, LnStates>,
+                          (const void*)k_leafnet_x3<20, LnStates, true>};
+    if (set_max_dynamic_lds(fns, 3, ln_lds_bytes(20)) != BK_OK) return BK_EHIP;
   }
   const LnHeads h{wp, bp, wv, bv, w1t, b1, w2, b2, P, pf, vout};
   hipStream_t s = (hipStream_t)stream;
   const h16x8* ws = reinterpret_cast<const h16x8*>(wstem);
   const h16x8* wt = reinterpret_cast<const h16x8*>(wtower);
   const LnStates in{reinterpret_cast<const uint32_t*>(states), status};
-  if (N == 20)
+  if (N == 20 && ln_edge())
+    hipLaunchKernelGGL((k_leafnet_x3<20, LnStates, true>), dim3(B), dim3(kLnThreads), ln_lds_bytes(20), s, in, ws, sstem,
+                       bstem, wt, stower, btower, bounds, nlayers, h, out);
+  else if (N == 20)
     hipLaunchKernelGGL((k_leafnet_x3<20, LnStates>), dim3(B), dim3(kLnThreads), ln_lds_bytes(20), s, in, ws, sstem, bstem,
                        wt, stower, btower, bounds, nlayers, h, out);
   else
@@ -728,8 +777,9 @@ int bk_leafnet_x3_rows(const bk_leafnet_args* nets, int nnets, const bk_arena_ro
   BK_REQUIRE(a0.P == kLnP, "bk_leafnet_x3_rows: the classic form takes P = 4 (np = 0)");
   BK_REQUIRE(bk_leafnet_x3_supported(a0.N), "bk_leafnet_x3_rows: N must be 14 or 20 (np = 0)");
   {
-    const void* fns[2] = {(const void*)k_leafnet_x3<14, LnRows>, (const void*)k_leafnet_x3<20, LnRows>};
-    if (set_max_dynamic_lds(fns, 2, ln_lds_bytes(20)) != BK_OK) return BK_EHIP;
+    const void* fns[3] = {(const void*)k_leafnet_x3<14, LnRows>, (const void*)k_leafnet_x3<20, LnRows>,
+                          (const void*)k_leafnet_x3<20, LnRows, true>};
+    if (set_max_dynamic_lds(fns, 3, ln_lds_bytes(20)) != BK_OK) return BK_EHIP;
   }
   const LnRows in = ln_rows_of(nets, nnets, rows, sim);
   const LnHeads h{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, a0.P, a0.pf, a0.vout};
@@ -737,7 +787,10 @@ int bk_leafnet_x3_rows(const bk_leafnet_args* nets, int nnets, const bk_arena_ro
   const h16x8* nw = nullptr;
   const float* nf = nullptr;
   float* out = nullptr;
-  if (a0.N == 20)
+  if (a0.N == 20 && ln_edge())
+    hipLaunchKernelGGL((k_leafnet_x3<20, LnRows, true>), dim3(rows->R), dim3(kLnThreads), ln_lds_bytes(20), s, in, nw, nf,
+                       nf, nw, nf, nf, nf, a0.nlayers, h, out);
+  else if (a0.N == 20)
     hipLaunchKernelGGL((k_leafnet_x3<20, LnRows>), dim3(rows->R), dim3(kLnThreads), ln_lds_bytes(20), s, in, nw, nf, nf,
                        nw, nf, nf, nf, a0.nlayers, h, out);
   else

@@ -5,6 +5,9 @@
 #include "../../include/blokus_engine.h"
 #include "ctx.h"
 
+#include <type_traits>
+#include <utility>
+
 namespace bk {
 // bk_leafnet_x3_rows for a net table of the np form (leafnet_np.hip); the table is validated
 int leafnet_np_rows(const bk_leafnet_args* nets, int nnets, const bk_arena_rows* rows, int sim, void* stream);
@@ -49,6 +52,8 @@ __host__ __device__ constexpr int ln_chunks(int cin) { return cin == 64 ? 18 : 3
 // a chunk load the first kLnPf of the next), so the LDS latency is never exposed at a chunk start.
 // The slot of group g is g % kLnSlots in every chunk, which needs NG % kLnSlots == 0: the board's
 // groups are padded with spare ones (all columns spare: halo reads, no writes) up to a multiple.
+// (ln_chunk_il_act, whose chunks differ in length, takes the slot from the position in the layer's
+// sequence of active (chunk, group) pairs instead.)
 #ifndef BK_LN_VACC
 #define BK_LN_VACC 0  // the MFMA accumulators in VGPRs (1: leafnet.hip, and leafnet_w3.hip, whose AGPRs hold U) or AGPRs (0)
 #endif
@@ -121,6 +126,124 @@ struct LnPixMap {
 };
 template <int N>
 __device__ constexpr LnPixMap<N> kLnPixMap{};
+
+// The edge-aware map of the 20x20 board (k_leafnet_x3<20, In, true>). Its last four groups each
+// hold 16 pixels of one board edge: row 0, row N-1 (columns 2..17), column 0, column N-1 (rows
+// 2..17). For the three taps that look outward over its edge such a group's whole B fragment is
+// halo, i.e. zero, and its MFMAs add only a*0 products: LnEdgeSched leaves them out. The other
+// 336 pixels fill groups 0..NG-5 by LnPixMap's greedy rule. The two row groups hit every slot
+// class mod 16 once; the two column groups (slots 22 apart: 6 mod 16) hit 8 classes twice, a
+// 2-way conflict on 2 of 25 groups that no lane order avoids (each ds_read_b128 lane group holds
+// all 16 columns of a group: leafnet.hip's plane blocks of the two k-groups share their banks).
+template <int N>
+struct LnEdgePixMap {
+  static constexpr int NN = N * N, NG = ln_groups(N), RS = ln_row(N), G0 = NG - 4;
+  static_assert(N == 20 && NG * 16 == NN, "LnEdgePixMap: the 20x20 board (no spare columns)");
+  // pixel i of edge group e (0 top, 1 bottom, 2 left, 3 right)
+  static constexpr int edge_pixel(int e, int i) {
+    return e == 0 ? 2 + i : e == 1 ? (N - 1) * N + 2 + i : e == 2 ? (2 + i) * N : (2 + i) * N + N - 1;
+  }
+  int slot[NG * 16];
+  constexpr LnEdgePixMap() : slot() {
+    bool used[NN] = {};
+    for (int i = 0; i < NG * 16; ++i) slot[i] = -1;
+    for (int e = 0; e < 4; ++e)
+      for (int i = 0; i < 16; ++i) {
+        const int p = edge_pixel(e, i);
+        used[p] = true;
+        slot[(G0 + e) * 16 + i] = (p / N + 1) * RS + p % N + 1;
+      }
+    for (int g = 0; g < G0; ++g)
+      for (int r = 0; r < 16; ++r)
+        for (int p = 0; p < NN; ++p) {
+          const int sl = (p / N + 1) * RS + p % N + 1;
+          if (!used[p] && sl % 16 == r) {
+            used[p] = true;
+            slot[g * 16 + r] = sl;
+            break;
+          }
+        }
+    int p = 0;
+    for (int i = 0; i < G0 * 16; ++i) {
+      if (slot[i] >= 0) continue;
+      while (p < NN && used[p]) ++p;
+      if (p == NN) break;
+      used[p] = true;
+      slot[i] = (p / N + 1) * RS + p % N + 1;
+    }
+  }
+};
+template <int N>
+__device__ constexpr LnEdgePixMap<N> kLnEdgePixMap{};
+
+// The tower's (group, chunk) schedule on LnEdgePixMap: chunk c of a 64 -> 64 conv is tap c / 2 =
+// (dy + 1) * 3 + (dx + 1); the top group skips dy < 0 (chunks 0-5), the bottom group dy > 0
+// (12-17), the left group dx < 0 (0, 1, 6, 7, 12, 13), the right group dx > 0 (4, 5, 10, 11, 16,
+// 17): 24 of a conv's 450 (group, chunk) pairs. active(c): the groups chunk c runs, as a bit mask;
+// first(c): those it runs first (the INIT form); pos0(c): the active pairs before chunk c.
+template <int N>
+struct LnEdgeSched {
+  static constexpr int NG = ln_groups(N), G0 = NG - 4, NC = ln_chunks(64);
+  static constexpr bool skips(int g, int c) {
+    const int t = c >> 1, dy = t / 3 - 1, dx = t % 3 - 1;
+    return g == G0 ? dy < 0 : g == G0 + 1 ? dy > 0 : g == G0 + 2 ? dx < 0 : g == G0 + 3 ? dx > 0 : false;
+  }
+  static constexpr unsigned active(int c) {
+    unsigned m = 0;
+    for (int g = 0; g < NG; ++g) m |= (skips(g, c) ? 0u : 1u) << g;
+    return m;
+  }
+  static constexpr unsigned first(int c) {
+    unsigned m = active(c);
+    for (int k = 0; k < c; ++k) m &= ~active(k);
+    return m;
+  }
+  static constexpr int pos0(int c) {
+    int n = 0;
+    for (int k = 0; k < c; ++k)
+      for (int g = 0; g < NG; ++g) n += skips(g, k) ? 0 : 1;
+    return n;
+  }
+};
+// the map is a bijection onto the board's pixels
+template <int N>
+constexpr bool ln_edge_map_is_bijection() {
+  constexpr int RS = ln_row(N), NG = ln_groups(N);
+  const LnEdgePixMap<N> m{};
+  bool seen[N * N] = {};
+  for (int i = 0; i < NG * 16; ++i) {
+    const int sl = m.slot[i];
+    if (sl < 0) return false;
+    const int r = sl / RS - 1, c = sl % RS - 1;
+    if (r < 0 || r >= N || c < 0 || c >= N || seen[r * N + c]) return false;
+    seen[r * N + c] = true;
+  }
+  return true;
+}
+// every pair the schedule skips reads only cells off the board (the zero halo) in all 16 columns;
+// every group runs in some chunk (its INIT), and the groups the ring reads ahead across a chunk
+// boundary (the first kLnPf) run in every chunk
+template <int N>
+constexpr bool ln_edge_sched_skips_only_halo() {
+  using S = LnEdgeSched<N>;
+  constexpr int RS = ln_row(N);
+  const LnEdgePixMap<N> m{};
+  unsigned ran = 0;
+  for (int c = 0; c < S::NC; ++c) {
+    const int t = c >> 1, dy = t / 3 - 1, dx = t % 3 - 1;
+    if ((S::active(c) & ((1u << kLnPf) - 1u)) != (1u << kLnPf) - 1u) return false;
+    ran |= S::active(c);
+    for (int g = 0; g < S::NG; ++g) {
+      if (!S::skips(g, c)) continue;
+      for (int n = 0; n < 16; ++n) {
+        const int sl = m.slot[g * 16 + n], r = sl / RS - 1 + dy, col = sl % RS - 1 + dx;
+        if (r >= 0 && r < N && col >= 0 && col < N) return false;
+      }
+    }
+  }
+  return ran == (1u << S::NG) - 1u;
+}
+
 template <int N>
 __device__ __forceinline__ int ln_pixel(int slot) {  // grid slot -> board pixel index
   return (slot / ln_row(N) - 1) * N + slot % ln_row(N) - 1;
@@ -376,6 +499,97 @@ __device__ __forceinline__ void ln_chunk_il(f32x4 (&acc)[NG], h16x8 ah, h16x8 al
               "i"(coff_next + HALF), "i"(2 * (kLnPf - 1)));
     }
   }
+}
+
+// The groups a chunk runs (bit mask ACT), in order, then the next chunk's first kLnPf groups as
+// NG + g (the ring reads on into them; they run in every chunk).
+template <int NG, unsigned ACT>
+struct LnActive {
+  int n;
+  int g[NG + kLnPf];
+  constexpr LnActive() : n(0), g() {
+    for (int k = 0; k < NG; ++k)
+      if ((ACT >> k) & 1u) g[n++] = k;
+    for (int k = 0; k < kLnPf; ++k) g[n + k] = NG + k;
+  }
+};
+
+// ln_chunk_il over the chunk's active groups only (LnEdgeSched): ACT the groups it runs, INIT those
+// of them that start their accumulator here, POS0 the layer's count of active (chunk, group) pairs
+// before this chunk. The ring slot of a pair is its position in that sequence mod kLnSlots (not
+// g % kLnSlots: the chunks differ in length); ln_prime fills positions 0..kLnPf-1. Each block
+// reads the pair kLnPf positions ahead, in this chunk or the next one's first groups. A group
+// left out keeps its accumulator: the products left out are a*0, whose sum +-0 changes no
+// accumulator that started at +0 and received only MFMA sums (never -0), so the sums are bitwise
+// ln_chunk_il's. Same lgkmcnt discipline: the wait inside each block, the caller's lgkmcnt(0)
+// after the last chunk, the ring registers written only by the asm blocks.
+template <int NG, unsigned ACT, unsigned INIT, int POS0, int HALF>
+__device__ __forceinline__ void ln_chunk_il_act(f32x4 (&acc)[NG], h16x8 ah, h16x8 al, const unsigned char* grid,
+                                                const int (&pb)[NG], int coff, int coff_next,
+                                                h16x8 (&rb)[kLnSlots][2]) {
+  constexpr LnActive<NG, ACT> A{};
+  static_assert((INIT & ~ACT) == 0u && A.n >= kLnPf, "ln_chunk_il_act: INIT groups run; the ring fits the chunk");
+  const unsigned gbase = (unsigned)(uintptr_t)grid;
+#pragma unroll
+  for (int i = 0; i < A.n; ++i) {
+    const int g = A.g[i], gp = A.g[i + kLnPf];
+    const int s = (POS0 + i) % kLnSlots, sp = (POS0 + i + kLnPf) % kLnSlots;
+    const unsigned addr = gbase + (unsigned)(gp < NG ? pb[gp] : pb[gp - NG]);
+    h16x8& n0 = rb[sp][0];
+    h16x8& n1 = rb[sp][1];
+    if (gp < NG) {
+      if ((INIT >> g) & 1u)
+        asm volatile(
+            "s_waitcnt lgkmcnt(%10)\n\t"
+            "v_mfma_f32_16x16x32_f16 %0, %3, %5, 0\n\t"
+            "ds_read_b128 %1, %7 offset:%8\n\t"
+            "v_mfma_f32_16x16x32_f16 %0, %4, %5, %0\n\t"
+            "ds_read_b128 %2, %7 offset:%9\n\t"
+            "v_mfma_f32_16x16x32_f16 %0, %3, %6, %0"
+            : BK_ACC_W(acc[g]), "=&v"(n0), "=&v"(n1)
+            : "v"(ah), "v"(al), "v"(rb[s][0]), "v"(rb[s][1]), "v"(addr), "i"(coff), "i"(coff + HALF), "i"(2 * (kLnPf - 1)));
+      else
+        asm volatile(
+            "s_waitcnt lgkmcnt(%10)\n\t"
+            "v_mfma_f32_16x16x32_f16 %0, %3, %5, %0\n\t"
+            "ds_read_b128 %1, %7 offset:%8\n\t"
+            "v_mfma_f32_16x16x32_f16 %0, %4, %5, %0\n\t"
+            "ds_read_b128 %2, %7 offset:%9\n\t"
+            "v_mfma_f32_16x16x32_f16 %0, %3, %6, %0"
+            : BK_ACC_RW(acc[g]), "=&v"(n0), "=&v"(n1)
+            : "v"(ah), "v"(al), "v"(rb[s][0]), "v"(rb[s][1]), "v"(addr), "i"(coff), "i"(coff + HALF), "i"(2 * (kLnPf - 1)));
+    } else {
+      if ((INIT >> g) & 1u)
+        asm volatile(
+            "s_waitcnt lgkmcnt(%10)\n\t"
+            "v_mfma_f32_16x16x32_f16 %0, %3, %5, 0\n\t"
+            "ds_read_b128 %1, %7 offset:%8\n\t"
+            "v_mfma_f32_16x16x32_f16 %0, %4, %5, %0\n\t"
+            "ds_read_b128 %2, %7 offset:%9\n\t"
+            "v_mfma_f32_16x16x32_f16 %0, %3, %6, %0"
+            : BK_ACC_W(acc[g]), "=&v"(n0), "=&v"(n1)
+            : "v"(ah), "v"(al), "v"(rb[s][0]), "v"(rb[s][1]), "v"(addr), "i"(coff_next), "i"(coff_next + HALF),
+              "i"(2 * (kLnPf - 1)));
+      else
+        asm volatile(
+            "s_waitcnt lgkmcnt(%10)\n\t"
+            "v_mfma_f32_16x16x32_f16 %0, %3, %5, %0\n\t"
+            "ds_read_b128 %1, %7 offset:%8\n\t"
+            "v_mfma_f32_16x16x32_f16 %0, %4, %5, %0\n\t"
+            "ds_read_b128 %2, %7 offset:%9\n\t"
+            "v_mfma_f32_16x16x32_f16 %0, %3, %6, %0"
+            : BK_ACC_RW(acc[g]), "=&v"(n0), "=&v"(n1)
+            : "v"(ah), "v"(al), "v"(rb[s][0]), "v"(rb[s][1]), "v"(addr), "i"(coff_next), "i"(coff_next + HALF),
+              "i"(2 * (kLnPf - 1)));
+    }
+  }
+}
+
+// f(integral_constant<int, 0>{}) ... f(integral_constant<int, NC - 1>{}): a chunk loop whose index
+// is a compile-time value (ln_chunk_il_act's schedule arguments)
+template <class F, int... Cs>
+__device__ __forceinline__ void ln_each_chunk(F&& f, std::integer_sequence<int, Cs...>) {
+  (f(std::integral_constant<int, Cs>{}), ...);
 }
 
 // the accumulators are written by MFMAs the compiler cannot see: wait out the MFMA write ->

@@ -29,12 +29,21 @@ print("bad boards", len(bad), bad[:20])
 if bad:
     e = err[bad[0]].amax(dim=0)  # [N, N]
     print("board", bad[0], "bad pixels", int((e / scale > 1e-5).sum()), "of", N * N)
-    # the kernel's pixel map (leafnet.hip LnPixMap): pixel -> (group, column)
+    # the kernel's pixel map (leafnet_common.h LnPixMap, or at N = 20 unless BK_LN_EDGE=0
+    # LnEdgePixMap: the last four groups are pieces of the four edges): pixel -> (group, column)
     RS = 18 if N == 14 else N + 2
     NG = ((N * N + 15) // 16 + 4) // 5 * 5
     used = [False] * (N * N)
     slot = [-1] * (NG * 16)
-    for gi in range(NG):
+    G0 = NG
+    if N == 20 and os.environ.get("BK_LN_EDGE", "1") != "0":
+        G0 = NG - 4
+        for e in range(4):
+            for i in range(16):
+                p = (2 + i, (N - 1) * N + 2 + i, (2 + i) * N, (2 + i) * N + N - 1)[e]
+                used[p] = True
+                slot[(G0 + e) * 16 + i] = (p // N + 1) * RS + p % N + 1
+    for gi in range(G0):
         for r in range(16):
             for p in range(N * N):
                 sl = (p // N + 1) * RS + p % N + 1
