@@ -27,6 +27,7 @@
 #include "../../include/blokus_engine.h"
 #include "ctx.h"
 
+#include <string>
 #include <type_traits>
 
 // the MFMA accumulators in VGPRs: the epilogue's VALU reads them without 100 v_accvgpr_read per
@@ -653,6 +654,71 @@ bool ln_edge() {
   return e ? atoi(e) != 0 : true;
 }
 
+// The refusals shared by bk_leafnet_x3_run and (per table entry, rows_form) bk_leafnet_x3_rows,
+// as "<who>: <what>": null operands, the N / P / np rules of the kernel family a.np names, the
+// depth and the alignments. out: bk_leafnet_x3_run's tower output (may be null). The rows form
+// runs one board per workgroup, so it does not look at np's boards_per_wg.
+int ln_check(const bk_leafnet_args& a, const char* who, const float* out, bool rows_form) {
+  const auto a4 = [](const void* p) { return ((uintptr_t)p & 3u) == 0; };
+  const auto a16 = [](const void* p) { return ((uintptr_t)p & 15u) == 0; };
+  const bool np = a.np != 0;
+  const char* bad = nullptr;
+  if (!a.obs == !a.states)
+    bad = "exactly one of obs and states must be set";
+  else if (!(a.wstem && a.sstem && a.bstem && a.wtower && a.stower && a.btower && a.bounds && a.wp && a.bp && a.wv &&
+             a.bv && a.w1t && a.b1 && a.w2 && a.b2 && a.pf && a.vout && a.P > 0))
+    bad = "null net operand";
+  else if (np && !(a.N == 7 || a.N == 14 || a.N == 20))
+    bad = "N must be 7, 14 or 20 (np form)";
+  else if (np && !(a.P >= 2 && a.P <= kMaxP))
+    bad = "P must be 2, 3 or 4 (np form)";
+  else if (np && !rows_form && !(a.np == 1 || a.np == 2 || (a.np == 5 && a.N == 7)))
+    bad = "np must be 0 or boards_per_wg + 1, boards_per_wg 0, 1 or (N = 7 only) 4";
+  // the classic planar form takes 8 planes whatever P: P reaches only the value head there
+  else if (!np && a.states && a.P != kLnP)
+    bad = "P must be 4 (the stem takes 8 observation planes; np = 0)";
+  else if (!np && !(a.N == 14 || a.N == 20))
+    bad = "N must be 14 or 20 (np = 0)";
+  else if (a.nlayers < 1)
+    bad = "at least one tower conv";
+  else if (a.states && !a4(a.states))
+    bad = "states must be 4-byte aligned";
+  else if (np && a.obs && !a4(a.obs))
+    bad = "obs must be 4-byte aligned";
+  else if (!(a16(a.wstem) && a16(a.wtower) && a16(a.sstem) && a16(a.bstem) && a16(a.stower) && a16(a.btower) &&
+             a16(a.wp) && a16(a.wv) && a16(out)))
+    bad = "16-byte aligned buffers";
+  if (!bad) return BK_OK;
+  set_error(std::string(who) + ": " + bad);
+  return BK_EINVAL;
+}
+
+// One launch of k_leafnet_x3 on `grid` workgroups: the weight set w, rows t0.. of a's outputs and
+// of the whole-batch tower output `out` (may be null). The rows form passes an empty w and
+// t0 = 0: the kernel takes each row's tree and weights from the table in `in`.
+template <typename In>  // const float* (the planes of row t0), LnStates (at row t0) or LnRows
+int ln_launch(In in, int grid, const bk_leafnet_args& a, const LnNet& w, int t0, float* out, void* stream) {
+  const void* fns[3] = {(const void*)k_leafnet_x3<14, In>, (const void*)k_leafnet_x3<20, In>,
+                        (const void*)k_leafnet_x3<20, In, true>};
+  if (set_max_dynamic_lds(fns, 3, ln_lds_bytes(20)) != BK_OK) return BK_EHIP;
+  const LnHeads h = ln_heads_of(a, w, t0);
+  float* xout = out ? out + (size_t)t0 * a.N * a.N * 64 : nullptr;
+  const dim3 g(grid), b(kLnThreads);
+  hipStream_t s = (hipStream_t)stream;
+  if (a.N == 20 && ln_edge())
+    hipLaunchKernelGGL((k_leafnet_x3<20, In, true>), g, b, ln_lds_bytes(20), s, in, w.wstem, w.sstem, w.bstem, w.wt, w.st,
+                       w.bt, w.bounds, a.nlayers, h, xout);
+  else if (a.N == 20)
+    hipLaunchKernelGGL((k_leafnet_x3<20, In>), g, b, ln_lds_bytes(20), s, in, w.wstem, w.sstem, w.bstem, w.wt, w.st,
+                       w.bt, w.bounds, a.nlayers, h, xout);
+  else
+    hipLaunchKernelGGL((k_leafnet_x3<14, In>), g, b, ln_lds_bytes(14), s, in, w.wstem, w.sstem, w.bstem, w.wt, w.st,
+                       w.bt, w.bounds, a.nlayers, h, xout);
+  return launch_check(std::is_same<In, LnRows>::value     ? "k_leafnet_x3 (rows)"
+                      : std::is_same<In, LnStates>::value ? "k_leafnet_x3 (states)"
+                                                          : "k_leafnet_x3");
+}
+
 }  // namespace
 }  // namespace bk
 
@@ -676,40 +742,26 @@ int bk_ln_stamps_clear() {
 }
 #endif
 
+int bk_leafnet_x3_run(const bk_leafnet_args* a, int t0, int n, float* out, void* stream) {
+  BK_REQUIRE(a && t0 >= 0 && n >= 0, "bk_leafnet_x3_run: bad argument");
+  if (int rc = ln_check(*a, "bk_leafnet_x3_run", out, false)) return rc;
+  if (n == 0) return BK_OK;
+  if (a->np) return leafnet_np_run(a, 1, nullptr, 0, t0, n, out, stream);
+  const LnNet w = ln_net_of(*a);
+  if (a->obs) return ln_launch(a->obs + (size_t)t0 * kStemCinX3 * a->N * a->N, n, *a, w, t0, out, stream);
+  return ln_launch(ln_states_of<LnStates>(*a, t0), n, *a, w, t0, out, stream);
+}
+
+// The four positional entries: wrappers that fill the struct and run rows [0, B).
 int bk_leafnet_x3(const float* obs, int B, int N, int cin, const void* wstem, const float* sstem, const float* bstem,
                   int nlayers, const void* wtower, const float* stower, const float* btower, const float* bounds,
                   const float* wp,
                   const float* bp, const float* wv, const float* bv, const float* w1t, const float* b1,
                   const float* w2, const float* b2, int P, float* pf, float* vout, float* out, void* stream) {
-  BK_REQUIRE(obs && wstem && sstem && bstem && wtower && stower && btower && bounds && B >= 0, "bad argument");
-  BK_REQUIRE(wp && bp && wv && bv && w1t && b1 && w2 && b2 && pf && vout && P > 0, "bad argument");
   BK_REQUIRE(cin == kStemCinX3, "bk_leafnet_x3: the stem takes 8 observation planes");
-  BK_REQUIRE(nlayers >= 1, "bk_leafnet_x3: at least one tower conv");
-  BK_REQUIRE(bk_leafnet_x3_supported(N), "bk_leafnet_x3: N must be 14 or 20");
-  const auto a16 = [](const void* p) { return ((uintptr_t)p & 15u) == 0; };
-  BK_REQUIRE(a16(wstem) && a16(wtower) && a16(sstem) && a16(bstem) && a16(stower) && a16(btower) && a16(wp) &&
-                 a16(wv) && a16(out),
-             "bk_leafnet_x3: 16-byte aligned buffers");
-  if (B == 0) return BK_OK;
-  {
-    const void* fns[3] = {(const void*)k_leafnet_x3<14, const float*>, (const void*)k_leafnet_x3<20, const float*>,
-                          (const void*)k_leafnet_x3<20, const float*, true>};
-    if (set_max_dynamic_lds(fns, 3, ln_lds_bytes(20)) != BK_OK) return BK_EHIP;
-  }
-  const LnHeads h{wp, bp, wv, bv, w1t, b1, w2, b2, P, pf, vout};
-  hipStream_t s = (hipStream_t)stream;
-  const h16x8* ws = reinterpret_cast<const h16x8*>(wstem);
-  const h16x8* wt = reinterpret_cast<const h16x8*>(wtower);
-  if (N == 20 && ln_edge())
-    hipLaunchKernelGGL((k_leafnet_x3<20, const float*, true>), dim3(B), dim3(kLnThreads), ln_lds_bytes(20), s, obs, ws,
-                       sstem, bstem, wt, stower, btower, bounds, nlayers, h, out);
-  else if (N == 20)
-    hipLaunchKernelGGL((k_leafnet_x3<20, const float*>), dim3(B), dim3(kLnThreads), ln_lds_bytes(20), s, obs, ws, sstem,
-                       bstem, wt, stower, btower, bounds, nlayers, h, out);
-  else
-    hipLaunchKernelGGL((k_leafnet_x3<14, const float*>), dim3(B), dim3(kLnThreads), ln_lds_bytes(14), s, obs, ws, sstem,
-                       bstem, wt, stower, btower, bounds, nlayers, h, out);
-  return launch_check("k_leafnet_x3");
+  const bk_leafnet_args a{obs, nullptr, nullptr, N,  P,  nlayers, wstem, sstem, bstem, wtower, stower, btower,
+                          bounds, wp,   bp,      wv, bv, w1t,     b1,    w2,    b2,    pf,     vout,   0};
+  return bk_leafnet_x3_run(&a, 0, B, out, stream);
 }
 
 int bk_leafnet_x3_states(const void* states, const int32_t* status, int B, int N, int P, const void* wstem,
@@ -717,37 +769,9 @@ int bk_leafnet_x3_states(const void* states, const int32_t* status, int B, int N
                          const float* stower, const float* btower, const float* bounds, const float* wp,
                          const float* bp, const float* wv, const float* bv, const float* w1t, const float* b1,
                          const float* w2, const float* b2, float* pf, float* vout, float* out, void* stream) {
-  BK_REQUIRE(states && wstem && sstem && bstem && wtower && stower && btower && bounds && B >= 0, "bad argument");
-  BK_REQUIRE(wp && bp && wv && bv && w1t && b1 && w2 && b2 && pf && vout, "bad argument");
-  BK_REQUIRE(P == kLnP, "bk_leafnet_x3_states: P must be 4 (the stem takes 8 observation planes)");
-  BK_REQUIRE(nlayers >= 1, "bk_leafnet_x3_states: at least one tower conv");
-  BK_REQUIRE(bk_leafnet_x3_supported(N), "bk_leafnet_x3_states: N must be 14 or 20");
-  BK_REQUIRE(((uintptr_t)states & 3u) == 0, "bk_leafnet_x3_states: states must be 4-byte aligned");
-  const auto a16 = [](const void* p) { return ((uintptr_t)p & 15u) == 0; };
-  BK_REQUIRE(a16(wstem) && a16(wtower) && a16(sstem) && a16(bstem) && a16(stower) && a16(btower) && a16(wp) &&
-                 a16(wv) && a16(out),
-             "bk_leafnet_x3_states: 16-byte aligned buffers");
-  if (B == 0) return BK_OK;
-  {
-    const void* fns[3] = {(const void*)k_leafnet_x3<14, LnStates>, (const void*)k_leafnet_x3<20, LnStates>,
-                          (const void*)k_leafnet_x3<20, LnStates, true>};
-    if (set_max_dynamic_lds(fns, 3, ln_lds_bytes(20)) != BK_OK) return BK_EHIP;
-  }
-  const LnHeads h{wp, bp, wv, bv, w1t, b1, w2, b2, P, pf, vout};
-  hipStream_t s = (hipStream_t)stream;
-  const h16x8* ws = reinterpret_cast<const h16x8*>(wstem);
-  const h16x8* wt = reinterpret_cast<const h16x8*>(wtower);
-  const LnStates in{reinterpret_cast<const uint32_t*>(states), status};
-  if (N == 20 && ln_edge())
-    hipLaunchKernelGGL((k_leafnet_x3<20, LnStates, true>), dim3(B), dim3(kLnThreads), ln_lds_bytes(20), s, in, ws, sstem,
-                       bstem, wt, stower, btower, bounds, nlayers, h, out);
-  else if (N == 20)
-    hipLaunchKernelGGL((k_leafnet_x3<20, LnStates>), dim3(B), dim3(kLnThreads), ln_lds_bytes(20), s, in, ws, sstem, bstem,
-                       wt, stower, btower, bounds, nlayers, h, out);
-  else
-    hipLaunchKernelGGL((k_leafnet_x3<14, LnStates>), dim3(B), dim3(kLnThreads), ln_lds_bytes(14), s, in, ws, sstem, bstem,
-                       wt, stower, btower, bounds, nlayers, h, out);
-  return launch_check("k_leafnet_x3 (states)");
+  const bk_leafnet_args a{nullptr, states, status, N,  P,  nlayers, wstem, sstem, bstem, wtower, stower, btower,
+                          bounds,  wp,     bp,     wv, bv, w1t,     b1,    w2,    b2,    pf,     vout,   0};
+  return bk_leafnet_x3_run(&a, 0, B, out, stream);
 }
 
 int bk_leafnet_x3_rows(const bk_leafnet_args* nets, int nnets, const bk_arena_rows* rows, int sim, void* stream) {
@@ -757,46 +781,16 @@ int bk_leafnet_x3_rows(const bk_leafnet_args* nets, int nnets, const bk_arena_ro
   if (nnets == 0 || rows->R == 0) return BK_OK;
   BK_REQUIRE(nets, "bk_leafnet_x3_rows: null net table");
   const bk_leafnet_args& a0 = nets[0];
-  const auto a16 = [](const void* p) { return ((uintptr_t)p & 15u) == 0; };
   for (int k = 0; k < nnets; ++k) {
     const bk_leafnet_args& a = nets[k];
     BK_REQUIRE(!a.obs && a.states && a.status, "bk_leafnet_x3_rows: states form only (states and status set, obs null)");
     BK_REQUIRE(a.states == a0.states && a.status == a0.status && a.pf == a0.pf && a.vout == a0.vout && a.N == a0.N &&
                    a.P == a0.P && a.nlayers == a0.nlayers && a.np == a0.np,
                "bk_leafnet_x3_rows: the nets must share states, status, pf, vout, N, P, nlayers and np");
-    BK_REQUIRE(a.wstem && a.sstem && a.bstem && a.wtower && a.stower && a.btower && a.bounds && a.wp && a.bp && a.wv &&
-                   a.bv && a.w1t && a.b1 && a.w2 && a.b2 && a.pf && a.vout,
-               "bk_leafnet_x3_rows: null net operand");
-    BK_REQUIRE(a16(a.wstem) && a16(a.wtower) && a16(a.sstem) && a16(a.bstem) && a16(a.stower) && a16(a.btower) &&
-                   a16(a.wp) && a16(a.wv),
-               "bk_leafnet_x3_rows: 16-byte aligned buffers");
+    if (int rc = ln_check(a, "bk_leafnet_x3_rows", nullptr, true)) return rc;
   }
-  BK_REQUIRE(a0.nlayers >= 1, "bk_leafnet_x3_rows: at least one tower conv");
-  BK_REQUIRE(((uintptr_t)a0.states & 3u) == 0, "bk_leafnet_x3_rows: states must be 4-byte aligned");
-  if (a0.np) return bk::leafnet_np_rows(nets, nnets, rows, sim, stream);
-  BK_REQUIRE(a0.P == kLnP, "bk_leafnet_x3_rows: the classic form takes P = 4 (np = 0)");
-  BK_REQUIRE(bk_leafnet_x3_supported(a0.N), "bk_leafnet_x3_rows: N must be 14 or 20 (np = 0)");
-  {
-    const void* fns[3] = {(const void*)k_leafnet_x3<14, LnRows>, (const void*)k_leafnet_x3<20, LnRows>,
-                          (const void*)k_leafnet_x3<20, LnRows, true>};
-    if (set_max_dynamic_lds(fns, 3, ln_lds_bytes(20)) != BK_OK) return BK_EHIP;
-  }
-  const LnRows in = ln_rows_of(nets, nnets, rows, sim);
-  const LnHeads h{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, a0.P, a0.pf, a0.vout};
-  hipStream_t s = (hipStream_t)stream;
-  const h16x8* nw = nullptr;
-  const float* nf = nullptr;
-  float* out = nullptr;
-  if (a0.N == 20 && ln_edge())
-    hipLaunchKernelGGL((k_leafnet_x3<20, LnRows, true>), dim3(rows->R), dim3(kLnThreads), ln_lds_bytes(20), s, in, nw, nf,
-                       nf, nw, nf, nf, nf, a0.nlayers, h, out);
-  else if (a0.N == 20)
-    hipLaunchKernelGGL((k_leafnet_x3<20, LnRows>), dim3(rows->R), dim3(kLnThreads), ln_lds_bytes(20), s, in, nw, nf, nf,
-                       nw, nf, nf, nf, a0.nlayers, h, out);
-  else
-    hipLaunchKernelGGL((k_leafnet_x3<14, LnRows>), dim3(rows->R), dim3(kLnThreads), ln_lds_bytes(14), s, in, nw, nf, nf,
-                       nw, nf, nf, nf, a0.nlayers, h, out);
-  return launch_check("k_leafnet_x3 (rows)");
+  if (a0.np) return leafnet_np_run(nets, nnets, rows, sim, 0, rows->R, nullptr, stream);
+  return ln_launch(ln_rows_of(nets, nnets, rows, sim), rows->R, a0, LnNet{}, 0, nullptr, stream);
 }
 
 }  // extern "C"

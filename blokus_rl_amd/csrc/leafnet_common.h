@@ -9,8 +9,13 @@
 #include <utility>
 
 namespace bk {
-// bk_leafnet_x3_rows for a net table of the np form (leafnet_np.hip); the table is validated
-int leafnet_np_rows(const bk_leafnet_args* nets, int nnets, const bk_arena_rows* rows, int sim, void* stream);
+// bk_leafnet_x3_run / bk_leafnet_x3_rows on the np kernels (leafnet_np.hip), the operands validated
+// by the caller (leafnet.hip ln_check). rows null: boards [t0, t0 + n) of nets[0], n > 0, with
+// out as bk_leafnet_x3_run's. Else the rows of the table `nets` at `sim`: one board per workgroup
+// whatever np's boards_per_wg says (the rows of a four-board workgroup could belong to different
+// nets); a board's outputs do not depend on the form, so they are bitwise those of the range.
+int leafnet_np_run(const bk_leafnet_args* nets, int nnets, const bk_arena_rows* rows, int sim, int t0, int n,
+                   float* out, void* stream);
 
 namespace {
 
@@ -651,6 +656,23 @@ __device__ __forceinline__ LnNet ln_pick(const LnNet (&n)[kLnMaxNets], int k) {
 #undef BK_LN_PICK
   return o;
 }
+// the kernel's weight set from the C-ABI's operands
+inline LnNet ln_net_of(const bk_leafnet_args& a) {
+  return LnNet{reinterpret_cast<const h16x8*>(a.wstem), a.sstem, a.bstem,
+               reinterpret_cast<const h16x8*>(a.wtower), a.stower, a.btower, a.bounds,
+               a.wp, a.bp, a.wv, a.bv, a.w1t, a.b1, a.w2, a.b2};
+}
+// the heads of w writing rows t0.. of a's pf and vout (the rows form: an empty w and t0 = 0, the
+// kernel takes the row's weights from its table and its outputs go to the row's tree)
+inline LnHeads ln_heads_of(const bk_leafnet_args& a, const LnNet& w, int t0) {
+  return LnHeads{w.wp, w.bp, w.wv, w.bv, w.w1t, w.b1, w.w2, w.b2, a.P, a.pf + (size_t)t0 * 2 * a.N * a.N,
+                 a.vout + (size_t)t0 * a.P};
+}
+// the packed-state input (LnStates / NpStates) at row t0 of a's states and status
+template <typename S>
+inline S ln_states_of(const bk_leafnet_args& a, int t0) {
+  return S{reinterpret_cast<const uint32_t*>(a.states) + (size_t)t0 * kStateWords, a.status ? a.status + t0 : nullptr};
+}
 // the kernel's table from the C-ABI's (validated by bk_leafnet_x3_rows)
 inline LnRows ln_rows_of(const bk_leafnet_args* nets, int nnets, const bk_arena_rows* rows, int sim) {
   LnRows in{};
@@ -662,12 +684,7 @@ inline LnRows ln_rows_of(const bk_leafnet_args* nets, int nnets, const bk_arena_
   in.sim = sim;
   in.nnets = nnets;
   in.ntrees = rows->T;
-  for (int k = 0; k < nnets; ++k) {
-    const bk_leafnet_args& a = nets[k];
-    in.nets[k] = LnNet{reinterpret_cast<const h16x8*>(a.wstem), a.sstem, a.bstem,
-                       reinterpret_cast<const h16x8*>(a.wtower), a.stower, a.btower, a.bounds,
-                       a.wp, a.bp, a.wv, a.bv, a.w1t, a.b1, a.w2, a.b2};
-  }
+  for (int k = 0; k < nnets; ++k) in.nets[k] = ln_net_of(nets[k]);
   return in;
 }
 // the row's tree and weight set, or -1 (workgroup-uniform) when the row has nothing to evaluate

@@ -675,16 +675,14 @@ __global__ __launch_bounds__(kLnThreads, 1) void k_leafnet_np(In in, int B, cons
 
 static_assert(NpGeo<20, 1>::kLds <= 160 * 1024, "k_leafnet_np<20>: LDS");
 
-// the launch of one instantiation
+// the launch of one instantiation: B boards with the weight set w and the heads h
 template <int N, int Q, typename In>
-int np_launch(In in, int B, const h16x8* ws, const float* sstem, const float* bstem, const h16x8* wt,
-              const float* stower, const float* btower, const float* bounds, int nlayers, const LnHeads& h, float* out,
-              hipStream_t s) {
+int np_launch(In in, int B, const LnNet& w, int nlayers, const LnHeads& h, float* out, hipStream_t s) {
   const void* fn = (const void*)k_leafnet_np<N, Q, In>;
   constexpr int kLds = NpGeo<N, Q>::kLds;
   if (set_max_dynamic_lds(&fn, 1, kLds) != BK_OK) return BK_EHIP;
-  hipLaunchKernelGGL((k_leafnet_np<N, Q, In>), dim3((B + Q - 1) / Q), dim3(kLnThreads), kLds, s, in, B, ws, sstem,
-                     bstem, wt, stower, btower, bounds, nlayers, h, out);
+  hipLaunchKernelGGL((k_leafnet_np<N, Q, In>), dim3((B + Q - 1) / Q), dim3(kLnThreads), kLds, s, in, B, w.wstem,
+                     w.sstem, w.bstem, w.wt, w.st, w.bt, w.bounds, nlayers, h, out);
   return launch_check("k_leafnet_np");
 }
 
@@ -707,34 +705,31 @@ int np_boards(int N, int B, int boards_per_wg) {
   return 5 * r1 >= 15 * r4 ? 4 : 1;
 }
 
-template <typename In>
-int np_dispatch(In in, int B, int N, int Q, const h16x8* ws, const float* sstem, const float* bstem, const h16x8* wt,
-                const float* stower, const float* btower, const float* bounds, int nlayers, const LnHeads& h,
-                float* out, hipStream_t s) {
-  if (N == 7 && Q == 4) return np_launch<7, 4, In>(in, B, ws, sstem, bstem, wt, stower, btower, bounds, nlayers, h, out, s);
-  if (N == 7) return np_launch<7, 1, In>(in, B, ws, sstem, bstem, wt, stower, btower, bounds, nlayers, h, out, s);
-  if (N == 14) return np_launch<14, 1, In>(in, B, ws, sstem, bstem, wt, stower, btower, bounds, nlayers, h, out, s);
-  return np_launch<20, 1, In>(in, B, ws, sstem, bstem, wt, stower, btower, bounds, nlayers, h, out, s);
+// One launch of k_leafnet_np on B boards, Q per workgroup: the weight set w, rows t0.. of a's
+// outputs and of the whole-batch tower output `out` (may be null). The rows form passes an empty
+// w, t0 = 0 and B = R workgroups of one board each (the kernel takes its board from the row table).
+template <typename In>  // const float* (the planes of row t0), NpStates (at row t0) or LnRows
+int np_run(In in, int B, int Q, const bk_leafnet_args& a, const LnNet& w, int t0, float* out, void* stream) {
+  const LnHeads h = ln_heads_of(a, w, t0);
+  float* xout = out ? out + (size_t)t0 * a.N * a.N * 64 : nullptr;
+  hipStream_t s = (hipStream_t)stream;
+  if constexpr (!std::is_same<In, LnRows>::value)
+    if (a.N == 7 && Q == 4) return np_launch<7, 4, In>(in, B, w, a.nlayers, h, xout, s);
+  if (a.N == 7) return np_launch<7, 1, In>(in, B, w, a.nlayers, h, xout, s);
+  if (a.N == 14) return np_launch<14, 1, In>(in, B, w, a.nlayers, h, xout, s);
+  return np_launch<20, 1, In>(in, B, w, a.nlayers, h, xout, s);
 }
 
 }  // namespace
 
-// bk_leafnet_x3_rows on the np form: one board per workgroup whatever np's boards_per_wg says (the
-// rows of a four-board workgroup could belong to different nets); a board's outputs do not depend
-// on the form, so they are bitwise those of bk_leafnet_x3_np_states
-int leafnet_np_rows(const bk_leafnet_args* nets, int nnets, const bk_arena_rows* rows, int sim, void* stream) {
-  const bk_leafnet_args& a0 = nets[0];
-  BK_REQUIRE(a0.N == 7 || a0.N == 14 || a0.N == 20, "bk_leafnet_x3_rows: N must be 7, 14 or 20 (np form)");
-  BK_REQUIRE(a0.P >= 2 && a0.P <= kMaxP, "bk_leafnet_x3_rows: P must be 2, 3 or 4 (np form)");
-  const LnRows in = ln_rows_of(nets, nnets, rows, sim);
-  const LnHeads h{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, a0.P, a0.pf, a0.vout};
-  const h16x8* nw = nullptr;
-  const float* nf = nullptr;
-  hipStream_t s = (hipStream_t)stream;
-  // B = R workgroups of one board each (the kernel takes its board from the row table)
-  if (a0.N == 7) return np_launch<7, 1, LnRows>(in, rows->R, nw, nf, nf, nw, nf, nf, nf, a0.nlayers, h, nullptr, s);
-  if (a0.N == 14) return np_launch<14, 1, LnRows>(in, rows->R, nw, nf, nf, nw, nf, nf, nf, a0.nlayers, h, nullptr, s);
-  return np_launch<20, 1, LnRows>(in, rows->R, nw, nf, nf, nw, nf, nf, nf, a0.nlayers, h, nullptr, s);
+int leafnet_np_run(const bk_leafnet_args* nets, int nnets, const bk_arena_rows* rows, int sim, int t0, int n,
+                   float* out, void* stream) {
+  const bk_leafnet_args& a = nets[0];
+  if (rows) return np_run(ln_rows_of(nets, nnets, rows, sim), rows->R, 1, a, LnNet{}, 0, nullptr, stream);
+  const int Q = np_boards(a.N, n, a.np - 1);
+  const LnNet w = ln_net_of(a);
+  if (a.obs) return np_run(a.obs + (size_t)t0 * 2 * a.P * a.N * a.N, n, Q, a, w, t0, out, stream);
+  return np_run(ln_states_of<NpStates>(a, t0), n, Q, a, w, t0, out, stream);
 }
 }  // namespace bk
 
@@ -744,29 +739,18 @@ extern "C" {
 
 int bk_leafnet_x3_np_supported(int N, int P) { return (N == 7 || N == 14 || N == 20) && P >= 2 && P <= kMaxP; }
 
+// Wrappers over bk_leafnet_x3_run (leafnet.hip): boards_per_wg folded into the struct's np.
 int bk_leafnet_x3_np(const float* obs, int B, int N, int cin, const void* wstem, const float* sstem,
                      const float* bstem, int nlayers, const void* wtower, const float* stower, const float* btower,
                      const float* bounds, const float* wp, const float* bp, const float* wv, const float* bv,
                      const float* w1t, const float* b1, const float* w2, const float* b2, int P, float* pf,
                      float* vout, float* out, int boards_per_wg, void* stream) {
-  BK_REQUIRE(obs && wstem && sstem && bstem && wtower && stower && btower && bounds && B >= 0, "bad argument");
-  BK_REQUIRE(wp && bp && wv && bv && w1t && b1 && w2 && b2 && pf && vout, "bad argument");
-  BK_REQUIRE(N == 7 || N == 14 || N == 20, "bk_leafnet_x3_np: N must be 7, 14 or 20");
-  BK_REQUIRE(P >= 2 && P <= kMaxP, "bk_leafnet_x3_np: P must be 2, 3 or 4");
   BK_REQUIRE(cin == 2 * P, "bk_leafnet_x3_np: the observation has 2 P planes");
-  BK_REQUIRE(nlayers >= 1, "bk_leafnet_x3_np: at least one tower conv");
   BK_REQUIRE(boards_per_wg == 0 || boards_per_wg == 1 || (boards_per_wg == 4 && N == 7),
              "bk_leafnet_x3_np: boards_per_wg must be 0, 1 or (N = 7 only) 4");
-  const auto a16 = [](const void* p) { return ((uintptr_t)p & 15u) == 0; };
-  BK_REQUIRE(a16(wstem) && a16(wtower) && a16(sstem) && a16(bstem) && a16(stower) && a16(btower) && a16(wp) &&
-                 a16(wv) && a16(out),
-             "bk_leafnet_x3_np: 16-byte aligned buffers");
-  BK_REQUIRE(((uintptr_t)obs & 3u) == 0, "bk_leafnet_x3_np: obs must be 4-byte aligned");
-  if (B == 0) return BK_OK;
-  const LnHeads h{wp, bp, wv, bv, w1t, b1, w2, b2, P, pf, vout};
-  return np_dispatch<const float*>(obs, B, N, np_boards(N, B, boards_per_wg), reinterpret_cast<const h16x8*>(wstem),
-                                   sstem, bstem, reinterpret_cast<const h16x8*>(wtower), stower, btower, bounds,
-                                   nlayers, h, out, (hipStream_t)stream);
+  const bk_leafnet_args a{obs, nullptr, nullptr, N,  P,  nlayers, wstem, sstem, bstem, wtower, stower, btower,
+                          bounds, wp,   bp,      wv, bv, w1t,     b1,    w2,    b2,    pf,     vout,   boards_per_wg + 1};
+  return bk_leafnet_x3_run(&a, 0, B, out, stream);
 }
 
 int bk_leafnet_x3_np_states(const void* states, const int32_t* status, int B, int N, int P, const void* wstem,
@@ -775,24 +759,11 @@ int bk_leafnet_x3_np_states(const void* states, const int32_t* status, int B, in
                             const float* bp, const float* wv, const float* bv, const float* w1t, const float* b1,
                             const float* w2, const float* b2, float* pf, float* vout, float* out, int boards_per_wg,
                             void* stream) {
-  BK_REQUIRE(states && wstem && sstem && bstem && wtower && stower && btower && bounds && B >= 0, "bad argument");
-  BK_REQUIRE(wp && bp && wv && bv && w1t && b1 && w2 && b2 && pf && vout, "bad argument");
-  BK_REQUIRE(N == 7 || N == 14 || N == 20, "bk_leafnet_x3_np_states: N must be 7, 14 or 20");
-  BK_REQUIRE(P >= 2 && P <= kMaxP, "bk_leafnet_x3_np_states: P must be 2, 3 or 4");
-  BK_REQUIRE(nlayers >= 1, "bk_leafnet_x3_np_states: at least one tower conv");
   BK_REQUIRE(boards_per_wg == 0 || boards_per_wg == 1 || (boards_per_wg == 4 && N == 7),
              "bk_leafnet_x3_np_states: boards_per_wg must be 0, 1 or (N = 7 only) 4");
-  BK_REQUIRE(((uintptr_t)states & 3u) == 0, "bk_leafnet_x3_np_states: states must be 4-byte aligned");
-  const auto a16 = [](const void* p) { return ((uintptr_t)p & 15u) == 0; };
-  BK_REQUIRE(a16(wstem) && a16(wtower) && a16(sstem) && a16(bstem) && a16(stower) && a16(btower) && a16(wp) &&
-                 a16(wv) && a16(out),
-             "bk_leafnet_x3_np_states: 16-byte aligned buffers");
-  if (B == 0) return BK_OK;
-  const LnHeads h{wp, bp, wv, bv, w1t, b1, w2, b2, P, pf, vout};
-  const NpStates in{reinterpret_cast<const uint32_t*>(states), status};
-  return np_dispatch<NpStates>(in, B, N, np_boards(N, B, boards_per_wg), reinterpret_cast<const h16x8*>(wstem), sstem,
-                               bstem, reinterpret_cast<const h16x8*>(wtower), stower, btower, bounds, nlayers, h, out,
-                               (hipStream_t)stream);
+  const bk_leafnet_args a{nullptr, states, status, N,  P,  nlayers, wstem, sstem, bstem, wtower, stower, btower,
+                          bounds,  wp,     bp,     wv, bv, w1t,     b1,    w2,    b2,    pf,     vout,   boards_per_wg + 1};
+  return bk_leafnet_x3_run(&a, 0, B, out, stream);
 }
 
 }  // extern "C"

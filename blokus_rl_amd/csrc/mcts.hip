@@ -852,29 +852,9 @@ static int pipe_prepare(bk_mcts* m) {
   return rc;
 }
 
-// the leaf net on trees [t0, t0 + n) of the whole-batch buffers in a: the public entries, on offset rows
+// the leaf net on trees [t0, t0 + n) of the whole-batch buffers in a
 static int pipe_net(const bk_leafnet_args* a, int t0, int n, void* stream) {
-  const size_t F = (size_t)2 * a->N * a->N;
-  float* pf = a->pf + (size_t)t0 * F;
-  float* vout = a->vout + (size_t)t0 * a->P;
-  if (a->np) {  // the other board shapes (leafnet_np.hip); outputs are batch-independent, so any range works
-    if (a->states)
-      return bk_leafnet_x3_np_states((const char*)a->states + (size_t)t0 * kStateBytes,
-                                     a->status ? a->status + t0 : nullptr, n, a->N, a->P, a->wstem, a->sstem,
-                                     a->bstem, a->nlayers, a->wtower, a->stower, a->btower, a->bounds, a->wp, a->bp,
-                                     a->wv, a->bv, a->w1t, a->b1, a->w2, a->b2, pf, vout, nullptr, a->np - 1, stream);
-    return bk_leafnet_x3_np(a->obs + (size_t)t0 * 2 * a->P * a->N * a->N, n, a->N, 2 * a->P, a->wstem, a->sstem,
-                            a->bstem, a->nlayers, a->wtower, a->stower, a->btower, a->bounds, a->wp, a->bp, a->wv,
-                            a->bv, a->w1t, a->b1, a->w2, a->b2, a->P, pf, vout, nullptr, a->np - 1, stream);
-  }
-  if (a->states)
-    return bk_leafnet_x3_states((const char*)a->states + (size_t)t0 * kStateBytes, a->status ? a->status + t0 : nullptr,
-                                n, a->N, a->P, a->wstem, a->sstem, a->bstem, a->nlayers, a->wtower, a->stower,
-                                a->btower, a->bounds, a->wp, a->bp, a->wv, a->bv, a->w1t, a->b1, a->w2, a->b2, pf,
-                                vout, nullptr, stream);
-  return bk_leafnet_x3(a->obs + (size_t)t0 * 2 * a->P * a->N * a->N, n, a->N, 2 * a->P, a->wstem, a->sstem, a->bstem,
-                       a->nlayers, a->wtower, a->stower, a->btower, a->bounds, a->wp, a->bp, a->wv, a->bv, a->w1t,
-                       a->b1, a->w2, a->b2, a->P, pf, vout, nullptr, stream);
+  return bk_leafnet_x3_run(a, t0, n, nullptr, stream);
 }
 
 int bk_mcts_sims_pipelined(bk_mcts* m, const bk_leafnet_args* net, int n_sims, int groups, int ring, const float* W,

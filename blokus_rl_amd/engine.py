@@ -145,6 +145,7 @@ _SIGS = {
                          + [_i, _vp, _vp, _vp, _i, _vp]),
     "bk_leafnet_x3_np_states": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp] + [_vp] * 8
                                 + [_vp, _vp, _vp, _i, _vp]),
+    "bk_leafnet_x3_run": (_i, [_vp, _i, _i, _vp, _vp]),
     "bk_leafnet_x3_rows": (_i, [_vp, _i, _vp, _i, _vp]),
     "bk_leafnet_w3_weight_bytes": (_i, []),
     "bk_leafnet_w3_supported": (_i, [_i]),
@@ -155,7 +156,8 @@ _LIB = None
 
 
 class LeafnetArgs(ctypes.Structure):
-    """bk_leafnet_args (include/blokus_engine.h): the leaf net's operands for bk_mcts_sims_pipelined."""
+    """bk_leafnet_args (include/blokus_engine.h): the leaf net's operands for bk_leafnet_x3_run,
+    bk_mcts_sims_pipelined and the net table of bk_leafnet_x3_rows."""
     _fields_ = ([("obs", _vp), ("states", _vp), ("status", _vp), ("N", _i), ("P", _i), ("nlayers", _i)]
                 + [(k, _vp) for k in ("wstem", "sstem", "bstem", "wtower", "stower", "btower", "bounds", "wp", "bp",
                                       "wv", "bv", "w1t", "b1", "w2", "b2", "pf", "vout")]

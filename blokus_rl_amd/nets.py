@@ -397,39 +397,27 @@ def net_math() -> str:
     return m
 
 
+def _leafnet_x3_run(model: "LeafResNet", B: int, want_out: bool, **inputs):
+    """One bk_leafnet_x3_run call on the B rows of inputs (leafnet_x3_args' obs, or states and
+    status) with fresh outputs: (pf, v[, tower output [B, 64, N, N] channels_last])."""
+    from .engine import _check, _stream, load_library
+
+    N, dev = model.board_size, model.x3_wstem.device
+    pf = torch.empty((B, 2 * N * N), dtype=torch.float32, device=dev)
+    v = torch.empty((B, model.f.value_fc2.out_features), dtype=torch.float32, device=dev)
+    out = torch.empty((B, 64, N, N), dtype=torch.float32, device=dev,
+                      memory_format=torch.channels_last) if want_out else None
+    a = leafnet_x3_args(model, pf, v, need_status=False, **inputs)
+    optr = None if out is None else ctypes.c_void_p(out.data_ptr())
+    _check(load_library().bk_leafnet_x3_run(ctypes.byref(a), 0, B, optr, _stream(dev)))
+    return (pf, v, out) if want_out else (pf, v)
+
+
 def leafnet_x3(obs: torch.Tensor, model: "LeafResNet", want_out: bool = False):
     """bk_leafnet_x3: the planar observation [B, 8, N, N] -> (policy features [B, 2*N*N], values
     [B, P][, tower output [B, 64, N, N] channels_last]) in one launch. A model whose x3 entry for
     N is "np" (LeafResNet.x3_entry: x3_boards "all") takes [B, 2P, N, N] through bk_leafnet_x3_np."""
-    from .engine import _check, _ptr, _stream, load_library
-
-    B, cin, N, _ = obs.shape
-    f = model.f
-    np_entry = model.x3_entry(N) == "np"
-    assert cin == (f.stem.in_channels if np_entry else 8) and obs.dtype == torch.float32 and obs.is_contiguous()
-    lib = load_library()
-    nl = 2 * len(f.blocks)
-    assert model.x3_wtower.numel() == nl * lib.bk_leafnet_x3_weight_bytes(64)
-    assert model.x3_wstem.numel() == lib.bk_leafnet_x3_weight_bytes(8)
-    P = f.value_fc2.out_features
-    pf = torch.empty((B, 2 * N * N), dtype=torch.float32, device=obs.device)
-    v = torch.empty((B, P), dtype=torch.float32, device=obs.device)
-    out = torch.empty((B, 64, N, N), dtype=torch.float32, device=obs.device,
-                      memory_format=torch.channels_last) if want_out else None
-    h = model.x3_heads
-    optr = None if out is None else ctypes.c_void_p(out.data_ptr())
-    if np_entry:
-        _check(lib.bk_leafnet_x3_np(
-            ctypes.c_void_p(obs.data_ptr()), B, N, cin, _ptr(model.x3_wstem), _ptr(model.x3_sstem), _ptr(h[0]), nl,
-            _ptr(model.x3_wtower), _ptr(model.x3_stower), _ptr(model.b_tower), _ptr(model.x3_bounds),
-            *[_ptr(t) for t in h[1:]], P, _ptr(pf), _ptr(v), optr, x3_pack(), _stream(obs.device)))
-        return (pf, v, out) if want_out else (pf, v)
-    _check(lib.bk_leafnet_x3(
-        ctypes.c_void_p(obs.data_ptr()), B, N, cin, _ptr(model.x3_wstem), _ptr(model.x3_sstem), _ptr(h[0]), nl,
-        _ptr(model.x3_wtower), _ptr(model.x3_stower), _ptr(model.b_tower), _ptr(model.x3_bounds),
-        *[_ptr(t) for t in h[1:]], P, _ptr(pf),
-        _ptr(v), optr, _stream(obs.device)))
-    return (pf, v, out) if want_out else (pf, v)
+    return _leafnet_x3_run(model, obs.shape[0], want_out, obs=obs)  # leafnet_x3_args checks obs against the model
 
 
 def leafnet_x3_states(states, status: torch.Tensor | None, model: "LeafResNet", want_out: bool = False):
@@ -438,50 +426,33 @@ def leafnet_x3_states(states, status: torch.Tensor | None, model: "LeafResNet", 
     (the search's leaf status) or None: rows whose status is not 1 are evaluated as the all-zero
     observation and their state bytes are not read. states may also be the device address (int)
     of a [B, 384] buffer the caller keeps alive (BatchedMCTS.leaf_states_ptr), with B = len(status)."""
-    from .engine import STATE_BYTES, _check, _ptr, _stream, load_library
+    from .engine import STATE_BYTES
 
-    f = model.f
     dev = model.x3_wstem.device
     if isinstance(states, torch.Tensor):
         assert states.dtype == torch.uint8 and states.dim() == 2 and states.shape[1] == STATE_BYTES
         assert states.is_contiguous() and states.device == dev
-        B, sptr = states.shape[0], ctypes.c_void_p(states.data_ptr())
+        B = states.shape[0]
     else:
         assert status is not None, "a raw states pointer needs status for the batch size"
-        B, sptr = status.shape[0], ctypes.c_void_p(int(states))
-    if status is not None:
-        assert status.dtype == torch.int32 and status.shape == (B,) and status.is_contiguous() and status.device == dev
-    N = model.board_size
-    lib = load_library()
-    nl = 2 * len(f.blocks)
-    assert model.x3_wtower.numel() == nl * lib.bk_leafnet_x3_weight_bytes(64)
-    assert model.x3_wstem.numel() == lib.bk_leafnet_x3_weight_bytes(8)
-    P = f.value_fc2.out_features
-    pf = torch.empty((B, 2 * N * N), dtype=torch.float32, device=dev)
-    v = torch.empty((B, P), dtype=torch.float32, device=dev)
-    out = torch.empty((B, 64, N, N), dtype=torch.float32, device=dev,
-                      memory_format=torch.channels_last) if want_out else None
-    h = model.x3_heads
-    optr = None if out is None else ctypes.c_void_p(out.data_ptr())
-    if model.x3_entry(N) == "np":
-        _check(lib.bk_leafnet_x3_np_states(
-            sptr, _ptr(status), B, N, f.stem.in_channels // 2, _ptr(model.x3_wstem), _ptr(model.x3_sstem),
-            _ptr(h[0]), nl, _ptr(model.x3_wtower), _ptr(model.x3_stower), _ptr(model.b_tower),
-            _ptr(model.x3_bounds), *[_ptr(t) for t in h[1:]], _ptr(pf), _ptr(v), optr, x3_pack(), _stream(dev)))
-        return (pf, v, out) if want_out else (pf, v)
-    _check(lib.bk_leafnet_x3_states(
-        sptr, _ptr(status), B, N, f.stem.in_channels // 2, _ptr(model.x3_wstem), _ptr(model.x3_sstem), _ptr(h[0]), nl,
-        _ptr(model.x3_wtower), _ptr(model.x3_stower), _ptr(model.b_tower), _ptr(model.x3_bounds),
-        *[_ptr(t) for t in h[1:]], _ptr(pf), _ptr(v), optr, _stream(dev)))
-    return (pf, v, out) if want_out else (pf, v)
+        B = status.shape[0]
+    return _leafnet_x3_run(model, B, want_out, states=states, status=status)  # leafnet_x3_args checks status
+
+
+# bk_leafnet_args' weight fields and the LeafResNet buffers that hold them (x3_head0..8: LeafResNet.x3_heads)
+_X3_OPERANDS = (("wstem", "x3_wstem"), ("sstem", "x3_sstem"), ("bstem", "x3_head0"), ("wtower", "x3_wtower"),
+                ("stower", "x3_stower"), ("btower", "b_tower"), ("bounds", "x3_bounds")) + tuple(
+                    (k, f"x3_head{i + 1}") for i, k in enumerate(("wp", "bp", "wv", "bv", "w1t", "b1", "w2", "b2")))
 
 
 def leafnet_x3_args(model: "LeafResNet", pf: torch.Tensor, v: torch.Tensor, obs: torch.Tensor | None = None,
-                    states=None, status: torch.Tensor | None = None):
+                    states=None, status: torch.Tensor | None = None, need_status: bool = True):
     """The operands of leafnet_x3(obs, model) or leafnet_x3_states(states, status, model) as one
-    bk_leafnet_args struct (engine.LeafnetArgs) for bk_mcts_sims_pipelined, with pf [B, 2*N*N] and
-    v [B, P] as the outputs. The struct holds raw addresses: the caller keeps model, obs / states,
-    status, pf and v alive while it is in use (a captured graph: as long as the graph)."""
+    bk_leafnet_args struct (engine.LeafnetArgs) for bk_leafnet_x3_run and bk_mcts_sims_pipelined,
+    with pf [B, 2*N*N] and v [B, P] as the outputs. The states form needs a status for the search
+    and the net table (need_status); bk_leafnet_x3_run alone also takes None (every row a leaf).
+    The struct holds raw addresses: the caller keeps model, obs / states, status, pf and v alive
+    while it is in use (a captured graph: as long as the graph)."""
     from .engine import LeafnetArgs, load_library
 
     assert (obs is None) != (states is None)
@@ -501,18 +472,19 @@ def leafnet_x3_args(model: "LeafResNet", pf: torch.Tensor, v: torch.Tensor, obs:
         assert obs.dtype == torch.float32 and obs.shape == (B, 2 * P, N, N) and obs.is_contiguous() and obs.device == dev
         a.obs = obs.data_ptr()
     else:
-        assert status is not None and status.dtype == torch.int32 and status.shape == (B,) and status.device == dev
+        assert status is not None or not need_status
+        if status is not None:
+            assert status.dtype == torch.int32 and status.shape == (B,)
+            assert status.is_contiguous() and status.device == dev
+            a.status = status.data_ptr()
         a.states = states.data_ptr() if isinstance(states, torch.Tensor) else int(states)
-        a.status = status.data_ptr()
     a.N, a.P, a.nlayers = N, P, nl
     a.np = x3_pack() + 1 if entry == "np" else 0  # bk_leafnet_x3_np[_states] with boards_per_wg = np - 1
-    h = model.x3_heads
-    tensors = {"wstem": model.x3_wstem, "sstem": model.x3_sstem, "bstem": h[0], "wtower": model.x3_wtower,
-               "stower": model.x3_stower, "btower": model.b_tower, "bounds": model.x3_bounds, "pf": pf, "vout": v}
-    tensors.update(zip(("wp", "bp", "wv", "bv", "w1t", "b1", "w2", "b2"), h[1:]))
-    for k, t in tensors.items():
+    a.pf, a.vout = pf.data_ptr(), v.data_ptr()
+    for field, name in _X3_OPERANDS:
+        t = getattr(model, name)
         assert t.is_contiguous() and t.device == dev
-        setattr(a, k, t.data_ptr())
+        setattr(a, field, t.data_ptr())
     return a
 
 
@@ -800,6 +772,14 @@ class LeafResNet(nn.Module):
         """Whether forward_states runs bk_leafnet_x3_states (else it observes and calls forward)."""
         return bool(self.x3 and net_math() == "x3" and self.x3_entry(self.board_size) is not None)
 
+    def _policy(self, pf, v):
+        """forward's result from the policy features pf and values v: them (features), else the
+        policy Linear's logits (normalize: their log-softmax) and v."""
+        if self.features:
+            return pf, v
+        logits = self.f.policy_out(pf)
+        return (F.log_softmax(logits, dim=1) if self.normalize else logits), v
+
     @torch.no_grad()
     def forward_states(self, states: torch.Tensor, status: torch.Tensor | None = None):
         """forward on the observation planes of packed states [B, 384] uint8, without the planes
@@ -808,11 +788,7 @@ class LeafResNet(nn.Module):
         (the search's stale leaf rows)."""
         f = self.f
         if self.takes_states():
-            pf, v = leafnet_x3_states(states, status, self)
-            if self.features:
-                return pf, v
-            logits = f.policy_out(pf)
-            return (F.log_softmax(logits, dim=1) if self.normalize else logits), v
+            return self._policy(*leafnet_x3_states(states, status, self))
         obs = _observe_states(states, self.board_size, f.value_fc2.out_features)
         if status is not None:
             obs = obs * (status == 1).view(-1, 1, 1, 1).to(obs.dtype)
@@ -829,27 +805,15 @@ class LeafResNet(nn.Module):
             math = net_math() if self.x3 else "f32"
             if math == "w3" and f.stem.in_channels == 8 and load_library().bk_leafnet_w3_supported(x.shape[2]):
                 # the tower as Winograd convolutions on split-f16 MFMA products (bk_leafnet_w3)
-                pf, v = leafnet_w3(x.float().contiguous(), self)
-                if self.features:
-                    return pf, v
-                logits = f.policy_out(pf)
-                return (F.log_softmax(logits, dim=1) if self.normalize else logits), v
+                return self._policy(*leafnet_w3(x.float().contiguous(), self))
             if math in ("x3", "w3") and self.x3_entry(x.shape[2]) is not None:
                 # the whole net in one launch on split-f16 MFMA products (bk_leafnet_x3)
-                pf, v = leafnet_x3(x.float().contiguous(), self)
-                if self.features:
-                    return pf, v
-                logits = f.policy_out(pf)
-                return (F.log_softmax(logits, dim=1) if self.normalize else logits), v
+                return self._policy(*leafnet_x3(x.float().contiguous(), self))
             fused = n and tower_enabled() and load_library().bk_tower_supported(x.shape[2])
             if fused and f.stem.in_channels == 8:
                 # stem conv, tower and heads in one launch (bk_resnet_stem_tower_heads)
-                pf, v = resnet_stem_tower_heads(x.float().contiguous(), self.w_stem_tower, self.u_tower, self.b_tower,
-                                                2 * n, f)
-                if self.features:
-                    return pf, v
-                logits = f.policy_out(pf)
-                return (F.log_softmax(logits, dim=1) if self.normalize else logits), v
+                return self._policy(*resnet_stem_tower_heads(x.float().contiguous(), self.w_stem_tower, self.u_tower,
+                                                             self.b_tower, 2 * n, f))
             x = conv3x3(x.float().contiguous(), self.w_stem, f.stem.bias, True)
             h = x
             if fused:
@@ -862,10 +826,7 @@ class LeafResNet(nn.Module):
                 if not n:
                     h = torch.relu(x + x)
                 pf, v = resnet_heads(h, f)
-            if self.features:
-                return pf, v
-            logits = f.policy_out(pf)
-            return (F.log_softmax(logits, dim=1) if self.normalize else logits), v
+            return self._policy(pf, v)
         # other widths: MIOpen convolutions (channels_last) with the bk_bias_act epilogue
         x = x.float().contiguous(memory_format=torch.channels_last)
         conv = lambda t, c: F.conv2d(t, c.weight, None, c.stride, c.padding)  # noqa: E731

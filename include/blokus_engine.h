@@ -560,7 +560,8 @@ int bk_resnet_stem_tower_heads(const float* obs, int B, int N, int cin, const fl
  * and nlayers x bk_leafnet_x3_weight_bytes(64) bytes), sstem [64] / stower [nlayers][64] the
  * inverse weight scales, bstem [64] / btower [nlayers][64] the biases, bounds [nlayers + 1][2]
  * per conv (stem first) (A, B) with |conv(x) + b| <= A max|x| + B (the output scale); head weights
- * as bk_resnet_heads. N = 14 or 20 (bk_leafnet_x3_supported), cin = 8, nlayers >= 1. */
+ * as bk_resnet_heads. N = 14 or 20 (bk_leafnet_x3_supported), cin = 8, nlayers >= 1. This entry
+ * and the three below are wrappers over bk_leafnet_x3_run, which refuses in their place. */
 int bk_leafnet_x3_weight_bytes(int cin);
 int bk_leafnet_x3_supported(int N);
 int bk_leafnet_x3(const float* obs, int B, int N, int cin, const void* wstem, const float* sstem, const float* bstem,
@@ -645,6 +646,17 @@ typedef struct bk_leafnet_args {
   float* vout;
   int np; /* 0: bk_leafnet_x3[_states]; boards_per_wg + 1 (1, 2 or 5): bk_leafnet_x3_np[_states] */
 } bk_leafnet_args;
+
+/* The leaf net on rows [t0, t0 + n) of the whole-batch buffers in a (obs or states + status, pf,
+ * vout): the one entry behind bk_leafnet_x3, bk_leafnet_x3_states, bk_leafnet_x3_np and
+ * bk_leafnet_x3_np_states, which are wrappers that fill the struct and run rows [0, B). Exactly
+ * one of a->obs and a->states must be set. a->np = 0: the classic kernel (N = 14 or 20; obs is
+ * [.][8][N][N] whatever P, states need P = 4); a->np = 1, 2 or 5: the np kernel with
+ * boards_per_wg = np - 1 (N = 7, 14 or 20, P = 2, 3 or 4, obs [.][2P][N][N]; 5 on N = 7 only).
+ * out (may be NULL): the whole batch's tower output [.][N][N][64], of which the same rows are
+ * written. Rows outside the range are neither read nor written; a row's outputs are bitwise
+ * those of a whole-batch run. n = 0 validates and launches nothing. */
+int bk_leafnet_x3_run(const bk_leafnet_args* a, int t0, int n, float* out, void* stream);
 
 /* n_sims simulations of every tree, the trees split into `groups` (1, 2 or 4) contiguous ranges
  * of ceil(T / groups) trees (empty ranges are skipped), each range a chain of its own:
