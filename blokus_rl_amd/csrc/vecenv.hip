@@ -97,9 +97,21 @@ __global__ __launch_bounds__(64) void k_vec_reset(DevPreset dp, uint32_t* states
   write_agent_view(dp, s, fa, m32, obs + (size_t)e * dp.N * dp.N, mask + (size_t)e * dp.W64);
 }
 
+// the masked-policy draw of the one-wave-per-env kernels (defined below, beside policy_draw16)
+__device__ __forceinline__ int policy_draw_wave(const DevPreset& dp, const uint32_t* m32, const float* __restrict__ row,
+                                                uint32_t* stage, int cap, bool zq, uint64_t& st, float& logp);
+
+// POL: 0 = the agent's id given (actions) or drawn uniformly; 1 / 2 = drawn from its policy logits
+// by policy_draw_wave over the mask the kernel builds from the state (2: with the reference
+// filter's zero-logit quirk), the id and its log-prob written to act_out / logp_out. The id then
+// goes the given id's way: A (no finite logit), like any id >= dp.A, is refused by place_action
+// before act_it is read and ends the episode as a loss.
+template <int POL>
 __global__ __launch_bounds__(64) void k_vec_step(DevPreset dp, uint32_t* states, uint64_t* rng,
                                                  const int32_t* actions, uint8_t* obs, uint64_t* mask,
-                                                 float* reward, int32_t* done) {
+                                                 float* reward, int32_t* done, const float* logits = nullptr,
+                                                 int32_t* act_out = nullptr, float* logp_out = nullptr,
+                                                 int cap = 0) {
   extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
   uint32_t* s = lds;
   uint64_t* fa = reinterpret_cast<uint64_t*>(lds + kStateWords);
@@ -113,7 +125,15 @@ __global__ __launch_bounds__(64) void k_vec_step(DevPreset dp, uint32_t* states,
   int fin = 0;
   // the agent's move (actions < 0: a uniformly random legal move, the benchmark's policy stand-in)
   int a = actions ? actions[e] : -1;
-  if (a < 0) {
+  if (POL) {
+    build_mask(dp, s, 0, fa, m32);
+    float lp;
+    a = policy_draw_wave(dp, m32, logits + (size_t)e * dp.A, m32 + dp.W32pad, cap, POL == 2, st, lp);
+    if (l == 0) {
+      act_out[e] = a;
+      logp_out[e] = lp;
+    }
+  } else if (a < 0) {
     build_mask(dp, s, 0, fa, m32);
     int K = 0;
     for (int w = l; w < dp.W32; w += kWave) K += __popc(m32[w]);
@@ -827,6 +847,196 @@ __global__ __launch_bounds__(kVecThreads) void k_vec_policy(const float* __restr
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// The same draw for the one-wave-per-env family (any 2-player preset: DevPreset at run time, the
+// agent's legal mask in LDS as m32), bit for bit policy_draw16's law (policy_sample of
+// oracle/vecenv_oracle.py: owner j < 16 holds mask words j, j + 16, ...). What the law leaves free
+// is spread over the 64 lanes; what it orders stays one f32 chain per owner:
+//   1. the legal ids are staged in LDS in owner-major order (owner 0's words, then owner 1's, ...):
+//      64 word positions per pass, offsets from a wave scan of the words' popcounts;
+//   2. all 64 lanes gather the staged ids' logits (K loads, balanced) and reduce the max;
+//   3. all 64 lanes turn them into p = bk_expf(x - m) in place (an id the zero rule excludes is
+//      carried as p = +0: it changes no bit of a non-negative sum, and the walk skips p = 0);
+//   4. lanes 0..15 add their owner's slice of p in order, then policy_draw16's scan / select; the
+//      selected owner walks its slice.
+// The no-candidate row (every id at -1e9) has integer sums: owner sums and the pick in closed form
+// (the walk's running sum is excl + c + 1 exactly, so the first c past the target is
+// floor(target) - excl). More legal ids than the staging holds (cap; BK_VEC_PCAP at launch):
+// the unstaged path — 64 lanes gather for the max by mask word, the owners re-read their words'
+// logits from global memory for the sum and the walk — the same arithmetic in the same order.
+// stage: p f32[cap] | owner starts int[20] | ids u16[cap]   (vec_pol_lds)
+constexpr int kVecPolCap = 1024;  // staged candidates per env (6 B each)
+
+__device__ __forceinline__ int policy_draw_wave(const DevPreset& dp, const uint32_t* m32,
+                                                const float* __restrict__ row, uint32_t* stage, int cap,
+                                                bool zq, uint64_t& st, float& logp) {
+  const int l = lane_id(), j = l & 15;
+  const int W64 = dp.W64, A = dp.A, NW = (W64 + 15) >> 4;
+  float* sp = reinterpret_cast<float*>(stage);
+  int* ostart = reinterpret_cast<int*>(stage + cap);
+  uint16_t* sid = reinterpret_cast<uint16_t*>(stage + cap + 20);
+  // ids >= A of the partial last word never count, whatever the caller's mask holds there
+  const uint64_t tail = (A & 63) ? (1ull << (A & 63)) - 1ull : ~0ull;
+  auto word = [&](int w) {
+    const uint64_t v = (uint64_t)m32[2 * w] | ((uint64_t)m32[2 * w + 1] << 32);
+    return w == W64 - 1 ? v & tail : v;
+  };
+  int K = 0;
+  for (int w = l; w < W64; w += kWave) K += __popcll(word(w));
+  K = wave_sum(K);
+  const bool staged = K <= cap;  // wave-uniform
+  float m = -INFINITY;
+  bool has = false;
+  if (staged) {
+    int base = 0;
+    for (int q0 = 0; q0 < 16 * NW; q0 += kWave) {  // position q = owner * NW + round
+      const int q = q0 + l, o = q / NW, i = q - o * NW, w = o + 16 * i;
+      uint64_t b = (o < 16 && w < W64) ? word(w) : 0ull;
+      const int cnt = __popcll(b);
+      const int incl = wave_incl_scan(cnt);
+      int pos = base + incl - cnt;
+      if (o < 16 && i == 0) ostart[o] = pos;
+      while (b) {
+        sid[pos++] = (uint16_t)(64 * w + __ffsll((unsigned long long)b) - 1);
+        b &= b - 1ull;
+      }
+      base += readlane_i(incl, kWave - 1);
+    }
+    if (l == 0) ostart[16] = K;
+    __syncthreads();
+    for (int k = l; k < K; k += kWave) {
+      const float x = row[sid[k]];
+      sp[k] = x;
+      if (!(zq && x == 0.0f)) {
+        m = fmaxf(m, x);
+        has = true;
+      }
+    }
+  } else {
+    for (int w = l; w < W64; w += kWave) {
+      uint64_t b = word(w);
+      while (b) {
+        const float x = row[64 * w + __ffsll((unsigned long long)b) - 1];
+        b &= b - 1ull;
+        if (!(zq && x == 0.0f)) {
+          m = fmaxf(m, x);
+          has = true;
+        }
+      }
+    }
+  }
+  const bool none = __ballot(has) == 0ull;  // wave-uniform
+  m = wave_max_f(m);
+  if (none) m = -1e9f;
+  if (staged && !none) {
+    for (int k = l; k < K; k += kWave) {  // each lane its own slots
+      const float x = sp[k];
+      sp[k] = (zq && x == 0.0f) ? 0.0f : bk_expf(x - m);
+    }
+  }
+  __syncthreads();
+  // owner o's candidates in order: f(p, id) -> stop
+  auto each = [&](int o, auto&& f) {
+    if (staged) {
+      const int k1 = ostart[o + 1];
+      for (int k = ostart[o]; k < k1; ++k)
+        if (f(sp[k], (int)sid[k])) return;
+    } else {
+      for (int w = o; w < W64; w += 16) {
+        uint64_t b = word(w);
+        while (b) {
+          const int id = 64 * w + __ffsll((unsigned long long)b) - 1;
+          b &= b - 1ull;
+          const float x = row[id];
+          if (f((zq && x == 0.0f) ? 0.0f : bk_expf(x - m), id)) return;
+        }
+      }
+    }
+  };
+  float s = 0.0f;
+  int nvalid = 0;  // ids of the owner's words (the no-candidate row)
+  if (l < 16) {
+    if (none) {
+      for (int w = l; w < W64; w += 16) nvalid += A - 64 * w >= 64 ? 64 : A - 64 * w;
+      s = (float)nvalid;  // = nvalid additions of 1.0f
+    } else {
+      each(l, [&](float p, int) {
+        s = s + p;
+        return false;
+      });
+    }
+  }
+  // lanes 0..15 are DPP row 0; the other rows scan zeros
+  float incl = s, t = dppf<0x111>(incl);
+  if (j >= 1) incl = t + incl;
+  t = dppf<0x112>(incl);
+  if (j >= 2) incl = t + incl;
+  t = dppf<0x114>(incl);
+  if (j >= 4) incl = t + incl;
+  t = dppf<0x118>(incl);
+  if (j >= 8) incl = t + incl;
+  const float S = __shfl(incl, 15);
+  const uint64_t z = mix64(st);  // = the env's splitmix64 output (rng_index's draw)
+  st += 0x9E3779B97F4A7C15ull;
+  const float target = S * ((float)(uint32_t)(z >> 40) * 0x1p-24f);
+  const uint32_t over = (uint32_t)(__ballot(incl > target) & 0xFFFFull);
+  const uint32_t pos = (uint32_t)(__ballot(s > 0.0f) & 0xFFFFull);
+  const int sel = over ? __ffs(over) - 1 : (pos ? 31 - __clz(pos) : 0);
+  const float excl = __shfl(incl, sel > 0 ? sel - 1 : 0);
+  int pick = -1;
+  if (l == sel) {
+    float acc = sel > 0 ? excl : 0.0f;
+    if (none) {
+      int c = (int)target - (int)acc;
+      c = c < 0 ? 0 : (c >= nvalid ? nvalid - 1 : c);
+      if (nvalid > 0) pick = 64 * (l + 16 * (c >> 6)) + (c & 63);
+    } else {
+      int last = -1;
+      each(l, [&](float p, int id) {
+        if (p > 0.0f) {
+          acc = acc + p;
+          last = id;
+          if (acc > target) {
+            pick = id;
+            return true;
+          }
+        }
+        return false;
+      });
+      if (pick < 0) pick = last;
+    }
+  }
+  pick = __shfl(pick, sel);
+  const float xp = none ? -1e9f : row[pick >= 0 ? pick : 0];
+  logp = pick >= 0 ? xp - (m + bk_logf(S)) : __int_as_float(0x7FC00000);
+  return pick >= 0 ? pick : A;
+}
+
+// k_vec_policy_wave: policy_draw_wave alone (mask words from HBM, as bk_vec_reset / bk_vec_step
+// leave them, copied to LDS as m32); one wave per env. lds = W32pad words | the staging.
+__global__ __launch_bounds__(64) void k_vec_policy_wave(DevPreset dp, const float* __restrict__ logits,
+                                                        const uint64_t* __restrict__ mask,
+                                                        uint64_t* __restrict__ rng, int zq, int cap,
+                                                        int32_t* __restrict__ act, float* __restrict__ logp) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+  uint32_t* m32 = lds;
+  const int e = blockIdx.x, l = lane_id();
+  for (int w = l; w < dp.W64; w += kWave) {
+    const uint64_t v = mask[(size_t)e * dp.W64 + w];
+    m32[2 * w] = (uint32_t)v;
+    m32[2 * w + 1] = (uint32_t)(v >> 32);
+  }
+  uint64_t st = rng[e];
+  __syncthreads();
+  float lp;
+  const int a = policy_draw_wave(dp, m32, logits + (size_t)e * dp.A, m32 + dp.W32pad, cap, zq != 0, st, lp);
+  if (l == 0) {
+    act[e] = a;
+    logp[e] = lp;
+    rng[e] = st;
+  }
+}
+
 }  // namespace
 }  // namespace bk
 
@@ -834,6 +1044,25 @@ using namespace bk;
 
 static size_t vec_lds(const DevPreset& dp) {
   return sizeof(uint32_t) * (size_t)(kStateWords + 2 * kMaxN + dp.W32pad);
+}
+// the wave draw's staging capacity: kVecPolCap, no more than the preset's ids; BK_VEC_PCAP=<n> lowers
+// it (A/B: rows with more than n legal ids take the unstaged path; 0 = every row)
+static int vec_pol_cap(const DevPreset& dp) {
+  int cap = dp.A < kVecPolCap ? dp.A : kVecPolCap;
+  const char* g = getenv("BK_VEC_PCAP");
+  if (g && *g) {
+    const int n = atoi(g);
+    cap = n < 0 ? 0 : (n < cap ? n : cap);
+  }
+  return cap;
+}
+// policy_draw_wave's staging behind the mask words: p f32[cap] | owner starts int[20] | ids u16[cap]
+static size_t vec_pol_lds(int cap) {
+  return sizeof(uint32_t) * (size_t)(cap + 20) + sizeof(uint16_t) * (size_t)((cap + 1) & ~1);
+}
+static bool vec_is_7x7(const DevPreset& dp) {  // the presets of k_vec_step7 / k_vec_policy
+  const char* g = getenv("BK_VEC_WAVE");       // A/B: the one-wave-per-env kernels on 7x7 too
+  return dp.N == 7 && (dp.num_pieces == 9 || dp.num_pieces == 21) && !(g && atoi(g));
 }
 
 extern "C" {
@@ -861,8 +1090,7 @@ int bk_vec_step(bk_ctx* c, void* states, uint64_t* rng, const int32_t* actions, 
   BK_REQUIRE(c->d_items, "host-only context (created with device < 0)");
   BK_REQUIRE(c->dp.P == 2, "the vector env is the 2-player preset");
   if (E == 0) return BK_OK;
-  const char* g = getenv("BK_VEC_WAVE");  // A/B: the one-wave-per-env kernel on 7x7 too
-  if (c->dp.N == 7 && (c->dp.num_pieces == 9 || c->dp.num_pieces == 21) && !(g && atoi(g))) {
+  if (vec_is_7x7(c->dp)) {
     const char* gl = getenv("BK_VEC_LANES");  // A/B: lanes per env (8 or 16)
     const int G = gl && atoi(gl) == 8 ? 8 : 16;
     const dim3 grid((E + kVecThreads / G - 1) / (kVecThreads / G));
@@ -878,19 +1106,26 @@ int bk_vec_step(bk_ctx* c, void* states, uint64_t* rng, const int32_t* actions, 
       hipLaunchKernelGGL((k_vec_step7<5, 8>), grid, dim3(kVecThreads), 0, st, sp, rng, actions, E, obs, mask, reward, done);
     return launch_check("k_vec_step7");
   }
-  hipLaunchKernelGGL(k_vec_step, dim3(E), dim3(kWave), vec_lds(c->dp), (hipStream_t)stream, c->dp,
-                     (uint32_t*)states, rng, actions, obs, mask, reward, done);
+  hipLaunchKernelGGL(k_vec_step<0>, dim3(E), dim3(kWave), vec_lds(c->dp), (hipStream_t)stream, c->dp,
+                     (uint32_t*)states, rng, actions, obs, mask, reward, done, (const float*)nullptr,
+                     (int32_t*)nullptr, (float*)nullptr, 0);
   return launch_check("k_vec_step");
 }
 
 int bk_vec_policy(bk_ctx* c, const float* logits, const uint64_t* mask, uint64_t* rng, int E, int zero_masked,
                   int32_t* actions, float* logp, void* stream) {
   BK_REQUIRE(c && logits && mask && rng && actions && logp && E >= 0, "bad argument");
-  BK_REQUIRE(c->dp.P == 2 && c->dp.N == 7 && (c->dp.num_pieces == 9 || c->dp.num_pieces == 21),
-             "policy sampling: the 2-player 7x7 presets (919 / 2522 ids)");
+  BK_REQUIRE(c->dp.P == 2, "policy sampling: the 2-player presets");
   if (E == 0) return BK_OK;
-  const dim3 grid((E + 15) / 16), block(kVecThreads);
   hipStream_t st = (hipStream_t)stream;
+  if (!vec_is_7x7(c->dp)) {  // one wave per env, any 2-player preset
+    BK_REQUIRE(c->dp.A <= 65535, "policy sampling: ids are staged as u16");
+    const int cap = vec_pol_cap(c->dp);
+    hipLaunchKernelGGL(k_vec_policy_wave, dim3(E), dim3(kWave), sizeof(uint32_t) * c->dp.W32pad + vec_pol_lds(cap), st,
+                       c->dp, logits, mask, rng, zero_masked, cap, actions, logp);
+    return launch_check("k_vec_policy_wave");
+  }
+  const dim3 grid((E + 15) / 16), block(kVecThreads);
   if (c->dp.num_pieces == 9) {
     if (zero_masked)
       hipLaunchKernelGGL((k_vec_policy<4, true>), grid, block, 0, st, logits, mask, rng, E, actions, logp);
@@ -910,12 +1145,24 @@ int bk_vec_step_policy(bk_ctx* c, void* states, uint64_t* rng, const float* logi
                        void* stream) {
   BK_REQUIRE(c && states && rng && logits && obs && mask && reward && done && actions && logp && E >= 0,
              "bad argument");
-  BK_REQUIRE(c->dp.P == 2 && c->dp.N == 7 && (c->dp.num_pieces == 9 || c->dp.num_pieces == 21),
-             "the fused policy step: the 2-player 7x7 presets (919 / 2522 ids)");
+  BK_REQUIRE(c->d_items, "host-only context (created with device < 0)");
+  BK_REQUIRE(c->dp.P == 2, "the fused policy step: the 2-player presets");
   if (E == 0) return BK_OK;
-  const dim3 grid((E + kVecThreads / 16 - 1) / (kVecThreads / 16));
   hipStream_t st = (hipStream_t)stream;
   uint32_t* sp = (uint32_t*)states;
+  if (!vec_is_7x7(c->dp)) {  // k_vec_step with the wave draw in front
+    BK_REQUIRE(c->dp.A <= 65535, "the fused policy step: ids are staged as u16");
+    const int cap = vec_pol_cap(c->dp);
+    const size_t lds = vec_lds(c->dp) + vec_pol_lds(cap);
+    if (zero_masked)
+      hipLaunchKernelGGL(k_vec_step<2>, dim3(E), dim3(kWave), lds, st, c->dp, sp, rng, (const int32_t*)nullptr, obs, mask,
+                         reward, done, logits, actions, logp, cap);
+    else
+      hipLaunchKernelGGL(k_vec_step<1>, dim3(E), dim3(kWave), lds, st, c->dp, sp, rng, (const int32_t*)nullptr, obs, mask,
+                         reward, done, logits, actions, logp, cap);
+    return launch_check("k_vec_step<policy>");
+  }
+  const dim3 grid((E + kVecThreads / 16 - 1) / (kVecThreads / 16));
 #define BK_SP(MC, P)                                                                                              \
   hipLaunchKernelGGL((k_vec_step7<MC, 16, P>), grid, dim3(kVecThreads), 0, st, sp, rng, (const int32_t*)nullptr, E, \
                      obs, mask, reward, done, logits, actions, logp)

@@ -3,8 +3,8 @@
 Rollouts never leave the GPU: BlokusVectorEnv steps all envs in one kernel and hands back the
 agent's legal-move bitmask; the rollout's draw (FilterLegalMoves + Categorical sample + log_prob of
 get_action_and_value, ppo/agent.py:27-42, 148-156) is one kernel over the actor's raw logits and
-that bitmask (bk_vec_policy) on the 7x7 presets that have it; every other board, and
-`device_sampling=False`, takes the torch Categorical path over bk_filter_legal; GAE is one kernel over
+that bitmask (bk_vec_policy) on the 7x7 presets that have it (on every 2-player preset under
+`policy_draw="all"` / BK_VEC_POLICY=all); every other board, and `device_sampling=False`, takes the torch Categorical path over bk_filter_legal; GAE is one kernel over
 the [T, E] rollout (bk_ppo_gae, the reference's float32 operation order). The update
 (`optimize_agent`) is the reference's clipped-surrogate PPO step — same minibatch order (it
 draws its shuffles from np.random exactly as the reference does, so a seeded run matches),
@@ -166,8 +166,10 @@ class PPOTrainer:
 
     def __init__(self, hparams: PPOHparams, device: str | torch.device | None = None,
                  device_sampling: bool | None = None, channels_last: bool = False, phase_timers: bool = False,
-                 device_convs: bool | None = None):
-        """device_sampling: the rollout's draw inside the env step (bk_vec_step_policy) instead of
+                 device_convs: bool | None = None, policy_draw: str | None = None):
+        """policy_draw: passed to BlokusVectorEnv ("classic" / "all"; None reads BK_VEC_POLICY): under
+        "all" every 2-player preset has the draw kernels, so device_sampling=None takes them there too;
+        device_sampling: the rollout's draw inside the env step (bk_vec_step_policy) instead of
         torch's Categorical over FilterLegalMoves; None (the default) takes it where the env's
         preset has the kernels (`envs.policy_kernels`: 7x7 with max_piece_cells 4 or 5) and the
         torch path on every other board; True on a preset without them is a ValueError here;
@@ -182,7 +184,8 @@ class PPOTrainer:
         self.hparams = hp = hparams
         self.phase_timers = phase_timers
         self.phase_s = {"rollout": 0.0, "gae": 0.0, "update": 0.0}
-        self.envs = BlokusVectorEnv(hp.num_envs, hp.board_size, hp.max_piece_cells, device=device)
+        self.envs = BlokusVectorEnv(hp.num_envs, hp.board_size, hp.max_piece_cells, device=device,
+                                    policy_draw=policy_draw)
         if device_sampling:
             self.envs.require_policy_kernels("PPOTrainer(device_sampling=True)")
         self.device_sampling = self.envs.policy_kernels if device_sampling is None else bool(device_sampling)

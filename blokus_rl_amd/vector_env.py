@@ -10,6 +10,7 @@ in a Python loop from `envs.get_attr("ai_possible_indexes")` and `FilterLegalMov
 from __future__ import annotations
 
 import ctypes
+import os
 
 import numpy as np
 import torch
@@ -19,15 +20,24 @@ from .engine import Engine, _check, _ptr
 
 class BlokusVectorEnv:
     def __init__(self, num_envs: int, board_size: int = 7, max_piece_cells: int = 4,
-                 device: str | torch.device | None = None):
+                 device: str | torch.device | None = None, policy_draw: str | None = None):
+        """policy_draw: which presets draw the agent's move on the device (`policy_kernels`).
+        "classic": the two 7x7 presets of k_vec_step7 / k_vec_policy only; "all": every 2-player
+        preset, the others through the one-wave-per-env draw (k_vec_policy_wave, and k_vec_step with
+        the draw in front). None reads BK_VEC_POLICY from the environment; the default is classic."""
+        if policy_draw is None:
+            policy_draw = os.environ.get("BK_VEC_POLICY", "") or "classic"
+        if policy_draw not in ("classic", "all"):
+            raise ValueError(f"policy_draw is 'classic' or 'all', not {policy_draw!r}")
+        self.policy_draw = policy_draw
         self.eng = Engine(board_size, 2, max_piece_cells, device=device)
         self.num_envs = E = num_envs
         dev = self.eng.device
         self.device = dev
         self.single_action_space_n = self.eng.A
-        # the masked-policy draw (bk_vec_policy / bk_vec_step_policy) exists for the 7x7 presets
-        # with 9 or 21 pieces (max_piece_cells 4 or 5) only
-        self.policy_kernels = self.eng.N == 7 and self.eng.num_pieces in (9, 21)
+        # the masked-policy draw (bk_vec_policy / bk_vec_step_policy) is taken on the 7x7 presets
+        # with 9 or 21 pieces (max_piece_cells 4 or 5); on every preset under policy_draw="all"
+        self.policy_kernels = policy_draw == "all" or (self.eng.N == 7 and self.eng.num_pieces in (9, 21))
         self.states = torch.empty((E, 384), dtype=torch.uint8, device=dev)
         self.rng = torch.zeros(E, dtype=torch.int64, device=dev)
         self.obs = torch.empty((E, board_size, board_size), dtype=torch.uint8, device=dev)
@@ -72,7 +82,8 @@ class BlokusVectorEnv:
     def require_policy_kernels(self, what: str):
         if not self.policy_kernels:
             raise ValueError(f"{what}: the device policy draw exists for the 7x7 presets with max_piece_cells 4 or 5 "
-                             f"only, not for board_size={self.eng.N}, max_piece_cells={self.eng.max_cells}")
+                             f"only, not for board_size={self.eng.N}, max_piece_cells={self.eng.max_cells}"
+                             " (policy_draw='all' or BK_VEC_POLICY=all takes it on every 2-player preset)")
 
     def sample_policy(self, logits: torch.Tensor, zero_masked: bool = True):
         """The agent's moves drawn from its policy on the device (bk_vec_policy): the rollout's

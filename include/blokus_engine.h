@@ -265,14 +265,19 @@ int bk_vec_step(bk_ctx* ctx, void* states, uint64_t* rng, const int32_t* actions
  * (the reference filter's quirk); with none, every id in [0, A) at -1e9 (uniform, as the
  * reference's all -1e9 row). actions[e] is drawn from the softmax over the candidates by an
  * inverse CDF on the env's splitmix64 stream (one draw; rng[e] advanced), logp[e] =
- * logits[e][a] - logsumexp (Categorical.log_prob). Feed actions to bk_vec_step. 2-player 7x7
- * presets (919 / 2522 ids). */
+ * logits[e][a] - logsumexp (Categorical.log_prob). Feed actions to bk_vec_step. Logits must be
+ * finite. Any 2-player preset: the 7x7 presets with 919 / 2522 ids on 16 lanes per env
+ * (k_vec_policy), every other one (and those two under BK_VEC_WAVE=1) on one wave per env
+ * (k_vec_policy_wave) — the same law, bit for bit. BK_VEC_PCAP=<n>, read at launch, lowers the
+ * wave kernel's LDS staging to n legal ids per env (A/B: rows with more take its unstaged path). */
 int bk_vec_policy(bk_ctx* ctx, const float* logits, const uint64_t* mask, uint64_t* rng, int E, int zero_masked,
                   int32_t* actions, float* logp, void* stream);
 /* bk_vec_step_policy: one rollout step in one launch — the agent's id drawn from its policy
  * logits exactly as bk_vec_policy draws it (same arithmetic, the legal mask taken from the step's
  * own legality pass instead of HBM), written to actions / logp, then bk_vec_step with that id:
- * the two launches' results bit for bit. The 2-player 7x7 presets. */
+ * the two launches' results bit for bit. Any 2-player preset: k_vec_step7 on the 7x7 presets with
+ * 919 / 2522 ids, k_vec_step with the wave draw in front on every other one (and on those two under
+ * BK_VEC_WAVE=1); an id >= the preset's ids (no finite logit) ends the episode as a loss. */
 int bk_vec_step_policy(bk_ctx* ctx, void* states, uint64_t* rng, const float* logits, int zero_masked, int E,
                        uint8_t* obs, uint64_t* mask, float* reward, int32_t* done, int32_t* actions, float* logp,
                        void* stream);
