@@ -59,6 +59,76 @@ struct LnStates {
 constexpr int kLnP = kStemCinX3 / 2;        // players of the 8-plane observation
 constexpr int kLnRowWords = kLnP * kMaxN;   // a state's board rows: plane p, row r = word p * kMaxN + r
 
+// FAST heads: the 1x1 convs' lane sums for the two policy channels at once, as packed f32 ops:
+// {y . w0, y . w1} with wx = {w0.x, w1.x} ... ww = {w0.w, w1.w}; each half is the plain
+// ((y.x w.x + y.y w.y) + y.z w.z) + y.w w.w (separate multiplies and adds, in that order).
+__device__ __forceinline__ f32x2 ln_dot2(f32x4 y, f32x2 wx, f32x2 wy, f32x2 wz, f32x2 ww) {
+  const f32x2 xy{y.x, y.y}, zw{y.z, y.w};
+  f32x2 t, u;
+  asm("v_pk_mul_f32 %0, %1, %2 op_sel:[0,0] op_sel_hi:[0,1]" : "=v"(t) : "v"(xy), "v"(wx));
+  asm("v_pk_mul_f32 %0, %1, %2 op_sel:[1,0] op_sel_hi:[1,1]" : "=v"(u) : "v"(xy), "v"(wy));
+  t = pk_add(t, u);
+  asm("v_pk_mul_f32 %0, %1, %2 op_sel:[0,0] op_sel_hi:[0,1]" : "=v"(u) : "v"(zw), "v"(wz));
+  t = pk_add(t, u);
+  asm("v_pk_mul_f32 %0, %1, %2 op_sel:[1,0] op_sel_hi:[1,1]" : "=v"(u) : "v"(zw), "v"(ww));
+  return pk_add(t, u);
+}
+// FAST heads: the sums over the wave's 4 k-groups (rows of 16 lanes) of four values at once. Row
+// r of the result holds v_r summed as (row 0 + row 1) + (row 2 + row 3), the order of the
+// one-value form a + a(lane ^ 16), then + (lane ^ 32) (x + y is the same sum in either order):
+// v_permlane16_swap pairs v0 with v1 and v2 with v3 (even rows keep the first value's rows 0 / 2
+// and take its rows 1 / 3 as the addend, odd rows the second value's), v_permlane32_swap then
+// pairs the two results' halves: 3 swaps and 3 adds for four values instead of 8 and 8.
+__device__ __forceinline__ float ln_quad_sum(float v0, float v1, float v2, float v3) {
+  const auto s01 = __builtin_amdgcn_permlane16_swap(__float_as_uint(v0), __float_as_uint(v1), false, false);
+  const float a = __uint_as_float(s01[0]) + __uint_as_float(s01[1]);
+  const auto s23 = __builtin_amdgcn_permlane16_swap(__float_as_uint(v2), __float_as_uint(v3), false, false);
+  const float c = __uint_as_float(s23[0]) + __uint_as_float(s23[1]);
+  const auto s = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(c), false, false);
+  return __uint_as_float(s[0]) + __uint_as_float(s[1]);
+}
+
+// FAST stem on a board without a lo plane: ln_chunk_hi with each group's B-fragment read (kLnPf
+// groups ahead) issued between its two MFMAs in one asm block, as ln_chunk_il does for the tower:
+// wait (lgkmcnt(kLnPf - 1): only the reads of the blocks between may still be in flight), MFMA,
+// read, MFMA. The stem's tap offset differs per lane (tap 4j + ks), so the read takes its whole
+// address from a register. Same discipline as ln_chunk_il: the ring registers are only read by
+// later blocks, after their wait, and the caller waits lgkmcnt(0) after the last chunk. Same
+// MFMAs on the same operands as ln_chunk_hi: the sums are bitwise equal.
+template <int NG, bool INIT>
+__device__ __forceinline__ void ln_chunk_hi_il(f32x4 (&acc)[NG], h16x8 ah, h16x8 al, const unsigned char* grid,
+                                               const int (&pb)[NG], int coff, int coff_next, h16x8 (&rb)[kLnSlots][2]) {
+  static_assert(NG % kLnSlots == 0, "ln_chunk_hi_il: the ring slot of a group must not depend on the chunk");
+  const unsigned gbase = (unsigned)(uintptr_t)grid;
+#pragma unroll
+  for (int g = 0; g < NG; ++g) {
+    const int gp = g + kLnPf;
+    const unsigned addr = gbase + (unsigned)(gp < NG ? pb[gp] + coff : pb[gp - NG] + coff_next);
+    h16x8& n0 = rb[gp % kLnSlots][0];
+    if (INIT)
+      asm volatile(
+          "s_waitcnt lgkmcnt(%6)\n\t"
+          "v_mfma_f32_16x16x32_f16 %0, %2, %4, 0\n\t"
+          "ds_read_b128 %1, %5\n\t"
+          "v_mfma_f32_16x16x32_f16 %0, %3, %4, %0"
+          : BK_ACC_W(acc[g]), "=&v"(n0)
+          : "v"(ah), "v"(al), "v"(rb[g % kLnSlots][0]), "v"(addr), "i"(kLnPf - 1));
+    else
+      asm volatile(
+          "s_waitcnt lgkmcnt(%6)\n\t"
+          "v_mfma_f32_16x16x32_f16 %0, %2, %4, %0\n\t"
+          "ds_read_b128 %1, %5\n\t"
+          "v_mfma_f32_16x16x32_f16 %0, %3, %4, %0"
+          : BK_ACC_RW(acc[g]), "=&v"(n0)
+          : "v"(ah), "v"(al), "v"(rb[g % kLnSlots][0]), "v"(addr), "i"(kLnPf - 1));
+  }
+}
+
+// Test hook of the FAST planes form (bk_ln_path_counts): while [0] is set, each workgroup counts the
+// stem it takes, [1] the two-product stem of a binary board, [2] the full stem. The flag is one
+// scalar load in flight under the observation loads.
+__device__ unsigned g_ln_paths[3];
+
 // STATES: the stem input is built from the board's state words instead of read as floats. Every
 // plane of the observation is binary (k_observe, env.hip), so the scaled board is 2^ex where a bit
 // is set and 0 elsewhere, ex = scale_exp(1) (scale_exp(0) on an all-zero board), and its lo half
@@ -74,7 +144,17 @@ constexpr int kLnRowWords = kLnP * kMaxN;   // a state's board rows: plane p, ro
 // halo (24 of a conv's 450 (group, chunk) pairs, 72 of 1350 MFMAs per wave with their 48
 // ds_read_b128). The products left out are a*0: every output is bitwise the full schedule's
 // (leafnet_common.h ln_chunk_il_act). The stem (4 taps per chunk: nothing to skip) only takes the map.
-template <int N, typename In, bool EDGE_A = false>  // In: const float* (planes), LnStates or LnRows
+//
+// FAST (the default: BK_LN_FAST): the shorter stem, prologue and heads below, every output bitwise
+// what the other instantiation computes. Planes form: a board whose 16 floats per lane are all
+// exactly 0.0f or 1.0f (every observation the search writes) has an all-zero lo plane, so it takes
+// the STATES form's two-product stem on the hi plane alone; any other board takes the full stem
+// (a workgroup-uniform branch). The halo is zeroed from per-thread constant slots, the STATES form
+// loads its state words without waiting for status[b], the stem's epilogue makes x0 and the split
+// halves in one pass and stores them as made (one barrier instead of two), and the heads reduce
+// four pixel groups' 1x1 sums at a time into a scratch indexed by grid slot, issue every later
+// global load before their first barrier and take one tanh for all value outputs.
+template <int N, typename In, bool EDGE_A = false, bool FAST = false>  // In: const float* (planes), LnStates or LnRows
 __global__ __launch_bounds__(kLnThreads, 1) void k_leafnet_x3(In in,
                                                               const h16x8* __restrict__ wstem_a,
                                                               const float* __restrict__ sstem_a,
@@ -140,11 +220,21 @@ __global__ __launch_bounds__(kLnThreads, 1) void k_leafnet_x3(In in,
   float xin[STATES ? 1 : PIX_IT][kStemCinX3];
   uint32_t sw = 0u;  // STATES: thread tid < kLnRowWords holds row word tid, thread kLnRowWords to_move
   bool live = true;
+  bool count_paths = false;
   if constexpr (STATES) {
     static_assert(kLnRowWords < kLnThreads && N <= kMaxN, "k_leafnet_x3: one state word per thread");
-    live = ROWS || !in.status || in.status[b] == 1;  // ROWS: a leaf, or the workgroup has returned
-    if (live && tid <= kLnRowWords) sw = in.states[b * kStateWords + (tid < kLnRowWords ? tid : kWToMove)];
+    if constexpr (FAST && !ROWS) {
+      // the state words do not wait for status[b]: both loads are in flight together, and the words
+      // of a board that is not a leaf (stale, but valid memory) are dropped
+      if (tid <= kLnRowWords) sw = in.states[b * kStateWords + (tid < kLnRowWords ? tid : kWToMove)];
+      live = !in.status || in.status[b] == 1;
+      if (!live) sw = 0u;
+    } else {
+      live = ROWS || !in.status || in.status[b] == 1;  // ROWS: a leaf, or the workgroup has returned
+      if (live && tid <= kLnRowWords) sw = in.states[b * kStateWords + (tid < kLnRowWords ? tid : kWToMove)];
+    }
   } else {
+    if constexpr (FAST) count_paths = g_ln_paths[0] != 0u;
     const float* __restrict__ ob = in + b * kStemCinX3 * NN;
 #pragma unroll
     for (int it = 0; it < PIX_IT; ++it) {
@@ -156,8 +246,33 @@ __global__ __launch_bounds__(kLnThreads, 1) void k_leafnet_x3(In in,
   // zero the halo of all 18 planes (rows 0 and N+1, columns 0 and N+1..RS-1; the only slots read
   // that no layer writes: interiors are written before they are read); STATES: 17, the stem
   // input has no lo plane
-  {
-    constexpr int kHaloCols = RS - N, kHalo = 2 * RS + N * kHaloCols;
+  constexpr int kHaloCols = RS - N, kHalo = 2 * RS + N * kHaloCols;
+  // FAST: thread tid owns halo slot tid % kHalo in the planes of its set tid / kHalo (plane = set,
+  // set + kHaloSets, ...): one decode per thread, then a store per plane at a constant stride. The
+  // planes form leaves out the stem's lo plane here: a binary board never reads it, any other
+  // board zeroes its halo beside the interior writes.
+  constexpr int kHaloSets = kLnThreads / kHalo;
+  static_assert(kHaloSets >= 1, "k_leafnet_x3: a plane's halo slots fit the workgroup");
+  int halo_off = -1;  // the thread's halo slot in a plane, bytes (-1: none)
+  if constexpr (FAST) {
+    const int set = tid / kHalo, k = tid - set * kHalo;
+    int row, col;
+    if (k < 2 * RS) {
+      row = k < RS ? 0 : N + 1;
+      col = k < RS ? k : k - RS;
+    } else {
+      const int h = k - 2 * RS, c = h % kHaloCols;
+      row = 1 + h / kHaloCols;
+      col = c == 0 ? 0 : N + c;
+    }
+    if (set < kHaloSets) {
+      halo_off = (row * RS + col) * 16;
+      unsigned char* q = lds + set * PL + halo_off;
+#pragma unroll
+      for (int j = 0; j * kHaloSets < 17; ++j)
+        if (j * kHaloSets + set < 17) *reinterpret_cast<u32x4*>(q + j * kHaloSets * PL) = u32x4{0u, 0u, 0u, 0u};
+    }
+  } else {
     for (int i = tid; i < (STATES ? 17 : 18) * kHalo; i += kLnThreads) {
       const int plane = i / kHalo, k = i - plane * kHalo;
       int row, col;
@@ -172,6 +287,7 @@ __global__ __launch_bounds__(kLnThreads, 1) void k_leafnet_x3(In in,
       *reinterpret_cast<u32x4*>(lds + plane * PL + (row * RS + col) * 16) = u32x4{0u, 0u, 0u, 0u};
     }
   }
+  LNSTAMP(32, __builtin_amdgcn_s_memtime());
 
   // the lane's grid slot in each group, in bytes (a spare column reads slot 0 of the halo: zeros),
   // and the mask of groups where the lane's column is a board pixel
@@ -223,6 +339,7 @@ __global__ __launch_bounds__(kLnThreads, 1) void k_leafnet_x3(In in,
   // ---- stem input: the planar observation [8][N][N] of the board, scaled by its maximum, split
   float max_obs;
   int ex;
+  bool binary = STATES;  // the stem input has no lo plane (workgroup-uniform)
   if constexpr (STATES) {
     // the board's row words (bits past the board dropped, as the observation drops them) and
     // to_move staged in the unused lo plane's space; the board maximum is 1 iff any plane has a
@@ -240,6 +357,7 @@ __global__ __launch_bounds__(kLnThreads, 1) void k_leafnet_x3(In in,
     }
     max_obs = block_max(any ? 1.0f : 0.0f, red + 8, wave, l);  // the barrier: zeroing and rows before the writes
     ex = scale_exp(max_obs);
+    LNSTAMP(36, __builtin_amdgcn_s_memtime());
     // a set cell's hi half: f16(2^ex), what split2 gives the planar form's 1.0f * 2^ex
     const unsigned one = __builtin_bit_cast(unsigned short, (_Float16)ldexpf(1.0f, ex));
     const uint32_t tm = rows[kLnRowWords];
@@ -264,22 +382,62 @@ __global__ __launch_bounds__(kLnThreads, 1) void k_leafnet_x3(In in,
     for (int it = 0; it < PIX_IT; ++it)
 #pragma unroll
       for (int c = 0; c < kStemCinX3; ++c) m = fmaxf(m, fabsf(xin[it][c]));
+    if constexpr (FAST) {
+      // the lane's floats are all exactly 0.0f or 1.0f (-0.0f and every other value fail); the
+      // workgroup's AND rides in the maximum's reduction (its own 4 floats of red, no barrier more)
+      bool bin = true;
+#pragma unroll
+      for (int it = 0; it < PIX_IT; ++it)
+#pragma unroll
+        for (int c = 0; c < kStemCinX3; ++c) {
+          const unsigned u = __float_as_uint(xin[it][c]);
+          bin = bin && (u == 0u || u == 0x3F800000u);
+        }
+      const bool wbin = __builtin_amdgcn_ballot_w64(!bin) == 0ull;
+      if (l == 0) red[12 + wave] = wbin ? 1.0f : 0.0f;
+    }
     max_obs = block_max(m, red + 8, wave, l);  // the barrier also orders the zeroing before the writes
     ex = scale_exp(max_obs);
+    LNSTAMP(36, __builtin_amdgcn_s_memtime());
+    if constexpr (FAST) {
+      const uint4 f = *reinterpret_cast<const uint4*>(red + 12);
+      binary = __builtin_amdgcn_readfirstlane((f.x & f.y & f.z & f.w) != 0u) != 0;
+      if (count_paths && tid == 0) atomicAdd(&g_ln_paths[binary ? 1 : 2], 1u);
+    }
+    if (FAST && binary) {
+      // x 2^ex is 0 or 2^ex, an f16 number: the hi half is the value, the lo half +0 in every cell
+      const _Float16 one = (_Float16)ldexpf(1.0f, ex);
 #pragma unroll
-    for (int it = 0; it < PIX_IT; ++it) {
-      const int p = tid + it * kLnThreads;
-      if (p < NN) {
-        unsigned h[4], o[4];
+      for (int it = 0; it < PIX_IT; ++it) {
+        const int p = tid + it * kLnThreads;
+        if (p < NN) {
+          unsigned h[4];
 #pragma unroll
-        for (int q = 0; q < 4; ++q) split2(ldexpf(xin[it][2 * q], ex), ldexpf(xin[it][2 * q + 1], ex), h[q], o[q]);
-        const u32x4 hi{h[0], h[1], h[2], h[3]}, lo{o[0], o[1], o[2], o[3]};
-        unsigned char* dst = sin + ((p / N + 1) * RS + p % N + 1) * 16;
-        *reinterpret_cast<u32x4*>(dst) = hi;
-        *reinterpret_cast<u32x4*>(dst + PL) = lo;
+          for (int q = 0; q < 4; ++q) {
+            const h16x2 v = h16x2{(_Float16)xin[it][2 * q], (_Float16)xin[it][2 * q + 1]} * h16x2{one, one};
+            h[q] = __builtin_bit_cast(unsigned, v);
+          }
+          *reinterpret_cast<u32x4*>(sin + ((p / N + 1) * RS + p % N + 1) * 16) = u32x4{h[0], h[1], h[2], h[3]};
+        }
+      }
+    } else {
+      if (FAST && tid < kHalo) *reinterpret_cast<u32x4*>(sin + PL + halo_off) = u32x4{0u, 0u, 0u, 0u};  // the lo plane's halo
+#pragma unroll
+      for (int it = 0; it < PIX_IT; ++it) {
+        const int p = tid + it * kLnThreads;
+        if (p < NN) {
+          unsigned h[4], o[4];
+#pragma unroll
+          for (int q = 0; q < 4; ++q) split2(ldexpf(xin[it][2 * q], ex), ldexpf(xin[it][2 * q + 1], ex), h[q], o[q]);
+          const u32x4 hi{h[0], h[1], h[2], h[3]}, lo{o[0], o[1], o[2], o[3]};
+          unsigned char* dst = sin + ((p / N + 1) * RS + p % N + 1) * 16;
+          *reinterpret_cast<u32x4*>(dst) = hi;
+          *reinterpret_cast<u32x4*>(dst + PL) = lo;
+        }
       }
     }
   }
+  LNSTAMP(33, __builtin_amdgcn_s_memtime());
   __syncthreads();
   LNSTAMP(1, __builtin_amdgcn_s_memtime());
 
@@ -291,14 +449,27 @@ __global__ __launch_bounds__(kLnThreads, 1) void k_leafnet_x3(In in,
       const int t = 4 * j + ks < 9 ? 4 * j + ks : 8;
       return ((t / 3 - 1) * RS + (t % 3 - 1)) * 16 + kBias - ks * 4 * PL;  // from ab: the stem grid has 2 planes
     };
-    if constexpr (STATES) {  // no lo plane: two products per chunk
+    if (binary) {  // no lo plane: two products per chunk
       ln_prime_hi<NG>(rb, sin, ab, toff(0));
+      if constexpr (FAST && kLnInterleave) {
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the primed reads: the blocks below count their own
 #pragma unroll
-      for (int j = 0; j < 3; ++j) {
-        if (j == 0)
-          ln_chunk_hi<NG, true>(acc, wsa[0][0], wsa[0][1], sin, ab, toff(0), toff(1), rb);
-        else
-          ln_chunk_hi<NG, false>(acc, wsa[j][0], wsa[j][1], sin, ab, toff(j), toff(j < 2 ? j + 1 : j), rb);
+        for (int j = 0; j < 3; ++j) {
+          if (j == 0)
+            ln_chunk_hi_il<NG, true>(acc, wsa[0][0], wsa[0][1], sin, ab, toff(0), toff(1), rb);
+          else
+            ln_chunk_hi_il<NG, false>(acc, wsa[j][0], wsa[j][1], sin, ab, toff(j), toff(j < 2 ? j + 1 : j), rb);
+        }
+        // the last chunk's read-ahead (untracked) lands before its registers are reused
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      } else {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+          if (j == 0)
+            ln_chunk_hi<NG, true>(acc, wsa[0][0], wsa[0][1], sin, ab, toff(0), toff(1), rb);
+          else
+            ln_chunk_hi<NG, false>(acc, wsa[j][0], wsa[j][1], sin, ab, toff(j), toff(j < 2 ? j + 1 : j), rb);
+        }
       }
     } else {
       ln_prime<NG, PL>(rb, sin, ab, toff(0));
@@ -395,7 +566,48 @@ __global__ __launch_bounds__(kLnThreads, 1) void k_leafnet_x3(In in,
 
   f32x4 x0[NG];
   float max_in;
-  {
+  if constexpr (FAST && kLnEpiWrite) {
+    // one pass: y (= x0[g], unscaled), y 2^ex_out (exact), its split halves, stored into the grid
+    // as they are made: no wave reads the activation planes before the barrier below (the stem
+    // reads its own two), so only the x0 stash, which reuses those two, waits for it; the stash is
+    // read back by its own thread alone
+    const int ex_out = out_exp(0, max_obs);
+    const int o = 2 * wave + (ks >> 1);
+    unsigned char* wbase = act + ((o & 3) * 4 + (o >> 2) * 2) * PL + (ks & 1) * 8;  // as write_act
+    const f32x2 s01{ldexpf(s_stem.x, -ex), ldexpf(s_stem.y, -ex)}, s23{ldexpf(s_stem.z, -ex), ldexpf(s_stem.w, -ex)};
+    const f32x2 b01{b_stem.x, b_stem.y}, b23{b_stem.z, b_stem.w};
+    const float up = ldexpf(1.0f, ex_out);
+    float mx = 0.0f;
+#pragma unroll
+    for (int g = 0; g < NG; ++g) {
+      f32x2 y01 = pk_fma(f32x2{acc[g][0], acc[g][1]}, s01, b01);
+      f32x2 y23 = pk_fma(f32x2{acc[g][2], acc[g][3]}, s23, b23);
+      y01 = f32x2{max_bits(y01.x, 0), max_bits(y01.y, 0)};
+      y23 = f32x2{max_bits(y23.x, 0), max_bits(y23.y, 0)};
+      if (is_valid(g)) mx = max3_abs(max3_abs(mx, y01.x, y01.y), y23.x, y23.y);
+      x0[g] = f32x4{y01.x, y01.y, y23.x, y23.y};
+      unsigned h0, h1, l0, l1;
+      split2(y01.x * up, y01.y * up, h0, l0);
+      split2(y23.x * up, y23.y * up, h1, l1);
+      if (is_valid(g)) {
+        *reinterpret_cast<u32x2*>(wbase + slot_b(g)) = u32x2{h0, h1};
+        *reinterpret_cast<u32x2*>(wbase + slot_b(g) + PL) = u32x2{l0, l1};
+      }
+    }
+#pragma unroll
+    for (int g = X0L; g < NG; ++g) asm volatile("" : "+a"(x0[g]));
+    post_max(mx, 0);
+    LNSTAMP(34, __builtin_amdgcn_s_memtime());
+    __syncthreads();  // the grid and the maxima are written; every wave is done with the stem's input planes
+    LNSTAMP(35, __builtin_amdgcn_s_memtime());
+#pragma unroll
+    for (int g = 0; g < X0L; ++g) {
+      x0s[g * kLnThreads + tid] = x0[g];
+      x0[g] = f32x4{0.f, 0.f, 0.f, 0.f};  // not kept in registers
+    }
+    max_in = board_max(0);
+    ex = ex_out;
+  } else {
     const int ex_out = out_exp(0, max_obs);
 #pragma unroll
     for (int g = 0; g < NG; ++g) x0[g] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -416,7 +628,9 @@ __global__ __launch_bounds__(kLnThreads, 1) void k_leafnet_x3(In in,
 #pragma unroll
     for (int g = X0L; g < NG; ++g) asm volatile("" : "+a"(x0[g]));
     post_max(mx, 0);
+    LNSTAMP(34, __builtin_amdgcn_s_memtime());
     __syncthreads();  // every wave is done with the stem's input planes (the x0 stash reuses them)
+    LNSTAMP(35, __builtin_amdgcn_s_memtime());
     write_act();
 #pragma unroll
     for (int g = 0; g < X0L; ++g) {
@@ -545,96 +759,227 @@ __global__ __launch_bounds__(kLnThreads, 1) void k_leafnet_x3(In in,
   }
 
   // ---- outputs: the tower output (optional) and the heads (blokus_nnet.py:146-150, BN folded)
+  f32x4 hw0, hw1, hwv;  // FAST: the 1x1 heads' weights, in flight across the barrier below
+  if constexpr (FAST) {
+    hw0 = *reinterpret_cast<const f32x4*>(hd.wp + oc);
+    hw1 = *reinterpret_cast<const f32x4*>(hd.wp + 64 + oc);
+    hwv = *reinterpret_cast<const f32x4*>(hd.wv + oc);
+  }
   if (xout) {
 #pragma unroll
     for (int g = 0; g < NG; ++g)
       if (is_valid(g))
         *reinterpret_cast<f32x4*>(xout + (b * NN + ln_pixel<N>(slot_b(g) / 16)) * 64 + oc) = acc[g];
   }
+  LNSTAMP(37, __builtin_amdgcn_s_memtime());
   __syncthreads();  // every wave is done with the activation grid: the heads' scratch reuses it
-  float* hp = reinterpret_cast<float*>(act);  // [NN][4 waves][3]
-  {
-    const f32x4 wp0 = *reinterpret_cast<const f32x4*>(hd.wp + oc);
-    const f32x4 wp1 = *reinterpret_cast<const f32x4*>(hd.wp + 64 + oc);
-    const f32x4 wvv = *reinterpret_cast<const f32x4*>(hd.wv + oc);
-#pragma unroll
-    for (int g = 0; g < NG; ++g) {
-      const f32x4 y = acc[g];
-      float d[3];
-      const f32x4* w[3] = {&wp0, &wp1, &wvv};
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        // the sum over the 4 k-groups: a + a(lane ^ 16), then + (lane ^ 32), as two VALU swaps
-        // (v_permlane16/32_swap) instead of LDS permutes; x + y is the same sum in either order
-        const float a = y.x * (*w[k]).x + y.y * (*w[k]).y + y.z * (*w[k]).z + y.w * (*w[k]).w;
-        const auto s16 = __builtin_amdgcn_permlane16_swap(__float_as_uint(a), __float_as_uint(a), false, false);
-        const float a16 = __uint_as_float(s16[0]) + __uint_as_float(s16[1]);
-        const auto s32 = __builtin_amdgcn_permlane32_swap(__float_as_uint(a16), __float_as_uint(a16), false, false);
-        d[k] = __uint_as_float(s32[0]) + __uint_as_float(s32[1]);
-      }
-      if (ks == 0 && is_valid(g)) {
-        float* dst = hp + (ln_pixel<N>(slot_b(g) / 16) * 4 + wave) * 3;
-        dst[0] = d[0];
-        dst[1] = d[1];
-        dst[2] = d[2];
-      }
-    }
-  }
-  __syncthreads();
-  LNSTAMP(20, __builtin_amdgcn_s_memtime());
-  // pf = relu(policy 1x1 conv + bp) (channel-major), vfeat = relu(value 1x1 conv + bv), then
-  // v = tanh(W2 relu(W1 vfeat + b1) + b2); the 4 waves sweep quarters of W1's inputs
-  float* vfeat = hp + NN * 12;
-  float* part = vfeat + NN;
-  // the head biases in registers first: read inside the loop, each was re-loaded after every pf
-  // store (the compiler cannot rule out aliasing), one dependent round trip per store
-  const float bp0 = hd.bp[0], bp1 = hd.bp[1], bv0 = hd.bv[0];
-  for (int i = tid; i < NN; i += kLnThreads) {
-    const float* q = hp + i * 12;
-    const float p0 = ((q[0] + q[3]) + q[6]) + q[9], p1 = ((q[1] + q[4]) + q[7]) + q[10],
-                pv = ((q[2] + q[5]) + q[8]) + q[11];
-    hd.pf[b * 2 * NN + i] = fmaxf(p0 + bp0, 0.0f);
-    hd.pf[b * 2 * NN + NN + i] = fmaxf(p1 + bp1, 0.0f);
-    vfeat[i] = fmaxf(pv + bv0, 0.0f);
-  }
-  __syncthreads();
-  {
-    // wave w: inputs [Q w, Q (w + 1)) of W1 (L2-resident), every load issued before the first FMA
-    constexpr int Q = NN / 4;
+  if constexpr (FAST) {
+    // The heads' scratch: hs[wave][grid slot][4] = the wave's 16-channel sums {policy 0, policy 1,
+    // value, -} of the pixel at that slot (16 B per entry: one store per lane, consecutive slots in
+    // consecutive bank groups), then vfeat and part. Four groups are reduced at a time
+    // (ln_quad_sum): k-group row r of the lanes ends with the sums of group g0 + r (the last
+    // group again past the end: the same values to the same place), so every lane stores.
+    constexpr int SL = (N + 2) * RS, Q = NN / 4;
     static_assert(NN % 4 == 0, "k_leafnet_x3: quarters of the value-MLP inputs");
+    static_assert(4 * SL * 16 + (NN + 4 * 64) * 4 <= 16 * PL, "k_leafnet_x3: the heads' scratch fits the activation planes");
+    unsigned char* hb = act + wave * (SL * 16);
+    const f32x2 wx{hw0.x, hw1.x}, wy{hw0.y, hw1.y}, wz{hw0.z, hw1.z}, ww{hw0.w, hw1.w};
+#pragma unroll
+    for (int g0 = 0; g0 < NG; g0 += 4) {
+      f32x2 p[4];
+      float q[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const f32x4 y = acc[g0 + r < NG ? g0 + r : NG - 1];
+        p[r] = ln_dot2(y, wx, wy, wz, ww);
+        q[r] = y.x * hwv.x + y.y * hwv.y + y.z * hwv.z + y.w * hwv.w;
+      }
+      const float d0 = ln_quad_sum(p[0].x, p[1].x, p[2].x, p[3].x);
+      const float d1 = ln_quad_sum(p[0].y, p[1].y, p[2].y, p[3].y);
+      const float d2 = ln_quad_sum(q[0], q[1], q[2], q[3]);
+      int sl = slot_b(g0);
+      bool ok = is_valid(g0);
+#pragma unroll
+      for (int r = 1; r < 4; ++r) {
+        const int g = g0 + r < NG ? g0 + r : NG - 1;
+        sl = ks == r ? slot_b(g) : sl;
+        ok = ks == r ? (bool)is_valid(g) : ok;
+      }
+      if (ok) *reinterpret_cast<f32x4*>(hb + sl) = f32x4{d0, d1, d2, 0.0f};
+    }
+    // every global load of the phases below is issued here, ahead of the barriers and of the pf
+    // stores (which the compiler cannot rule out as aliases): the head biases, the wave's quarter
+    // of W1 (L2-resident), and wave 0's W2 rows, b2 and b1
+    const float bp0 = hd.bp[0], bp1 = hd.bp[1], bv0 = hd.bv[0];
     const int q0 = Q * wave;
+    // (as buffer loads with immediate row offsets the Q loads took ~1k cycles longer: measured, dropped)
     float w[Q];
 #pragma unroll
     for (int k = 0; k < Q; ++k) w[k] = hd.w1t[(size_t)(q0 + k) * 64 + l];
-    float a0 = 0.f, a1 = 0.f;
-    int k = 0;
+    float w2[kMaxP], b2[kMaxP], b1 = 0.0f;
 #pragma unroll
-    for (; k + 10 <= Q; k += 10) {
+    for (int q = 0; q < kMaxP; ++q) w2[q] = b2[q] = 0.0f;
+    if (wave == 0) {
 #pragma unroll
-      for (int u = 0; u < 10; u += 2) {
-        a0 += w[k + u] * vfeat[q0 + k + u];
-        a1 += w[k + u + 1] * vfeat[q0 + k + u + 1];
+      for (int q = 0; q < kMaxP; ++q) {
+        w2[q] = q < hd.P ? hd.w2[q * 64 + l] : 0.0f;
+        b2[q] = q < hd.P ? hd.b2[q] : 0.0f;
+      }
+      b1 = hd.b1[l];
+    }
+    __syncthreads();
+    LNSTAMP(20, __builtin_amdgcn_s_memtime());
+    // pf = relu(policy 1x1 conv + bp) (channel-major), vfeat = relu(value 1x1 conv + bv): the
+    // waves' sums added as ((w0 + w1) + w2) + w3
+    float* vfeat = reinterpret_cast<float*>(act + 4 * SL * 16);
+    float* part = vfeat + NN;
+    for (int i = tid; i < NN; i += kLnThreads) {
+      const unsigned char* q = act + ((i / N + 1) * RS + i % N + 1) * 16;
+      const f32x4 a0 = *reinterpret_cast<const f32x4*>(q), a1 = *reinterpret_cast<const f32x4*>(q + SL * 16),
+                  a2 = *reinterpret_cast<const f32x4*>(q + 2 * SL * 16), a3 = *reinterpret_cast<const f32x4*>(q + 3 * SL * 16);
+      const float p0 = ((a0.x + a1.x) + a2.x) + a3.x, p1 = ((a0.y + a1.y) + a2.y) + a3.y,
+                  pv = ((a0.z + a1.z) + a2.z) + a3.z;
+      hd.pf[b * 2 * NN + i] = fmaxf(p0 + bp0, 0.0f);
+      hd.pf[b * 2 * NN + NN + i] = fmaxf(p1 + bp1, 0.0f);
+      vfeat[i] = fmaxf(pv + bv0, 0.0f);
+    }
+    __syncthreads();
+    LNSTAMP(38, __builtin_amdgcn_s_memtime());
+    {
+      // v = tanh(W2 relu(W1 vfeat + b1) + b2); wave w: inputs [Q w, Q (w + 1)) of W1, its vfeat
+      // quarter read 16 B at a time where the quarters are 16-B aligned; the sums in the order of
+      // the other code (a0 even, a1 odd inputs in blocks of 10, the rest into a0)
+      float vf[Q];
+      if constexpr (Q % 4 == 0) {
+#pragma unroll
+        for (int k = 0; k < Q; k += 4) {
+          const f32x4 t = *reinterpret_cast<const f32x4*>(vfeat + q0 + k);
+          vf[k] = t.x;
+          vf[k + 1] = t.y;
+          vf[k + 2] = t.z;
+          vf[k + 3] = t.w;
+        }
+      } else {
+#pragma unroll
+        for (int k = 0; k < Q; ++k) vf[k] = vfeat[q0 + k];
+      }
+      float a0 = 0.f, a1 = 0.f;
+      int k = 0;
+#pragma unroll
+      for (; k + 10 <= Q; k += 10) {
+#pragma unroll
+        for (int u = 0; u < 10; u += 2) {
+          a0 += w[k + u] * vf[k + u];
+          a1 += w[k + u + 1] * vf[k + u + 1];
+        }
+      }
+#pragma unroll
+      for (; k < Q; ++k) a0 += w[k] * vf[k];
+      part[wave * 64 + l] = a0 + a1;
+    }
+    __syncthreads();
+    LNSTAMP(39, __builtin_amdgcn_s_memtime());
+    if (wave == 0) {
+      const float h = fmaxf(((part[l] + part[64 + l]) + (part[128 + l] + part[192 + l])) + b1, 0.0f);
+      // every output's sum first, then one tanh: lane q takes output q's sum and bias and stores it
+      float x = 0.0f;
+#pragma unroll
+      for (int q = 0; q < kMaxP; ++q) {
+        if (q < hd.P) {
+          const float sq = wave_sum_f(w2[q] * h) + b2[q];
+          x = l == q ? sq : x;
+        }
+      }
+      const float t = tanhf(x);
+      if (l < hd.P) hd.v[b * hd.P + l] = t;
+    }
+  } else {
+    float* hp = reinterpret_cast<float*>(act);  // [NN][4 waves][3]
+    {
+      const f32x4 wp0 = *reinterpret_cast<const f32x4*>(hd.wp + oc);
+      const f32x4 wp1 = *reinterpret_cast<const f32x4*>(hd.wp + 64 + oc);
+      const f32x4 wvv = *reinterpret_cast<const f32x4*>(hd.wv + oc);
+#pragma unroll
+      for (int g = 0; g < NG; ++g) {
+        const f32x4 y = acc[g];
+        float d[3];
+        const f32x4* w[3] = {&wp0, &wp1, &wvv};
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+          // the sum over the 4 k-groups: a + a(lane ^ 16), then + (lane ^ 32), as two VALU swaps
+          // (v_permlane16/32_swap) instead of LDS permutes; x + y is the same sum in either order
+          const float a = y.x * (*w[k]).x + y.y * (*w[k]).y + y.z * (*w[k]).z + y.w * (*w[k]).w;
+          const auto s16 = __builtin_amdgcn_permlane16_swap(__float_as_uint(a), __float_as_uint(a), false, false);
+          const float a16 = __uint_as_float(s16[0]) + __uint_as_float(s16[1]);
+          const auto s32 = __builtin_amdgcn_permlane32_swap(__float_as_uint(a16), __float_as_uint(a16), false, false);
+          d[k] = __uint_as_float(s32[0]) + __uint_as_float(s32[1]);
+        }
+        if (ks == 0 && is_valid(g)) {
+          float* dst = hp + (ln_pixel<N>(slot_b(g) / 16) * 4 + wave) * 3;
+          dst[0] = d[0];
+          dst[1] = d[1];
+          dst[2] = d[2];
+        }
       }
     }
-#pragma unroll
-    for (; k < Q; ++k) a0 += w[k] * vfeat[q0 + k];
-    part[wave * 64 + l] = a0 + a1;
-  }
-  __syncthreads();
-  if (wave == 0) {
-    // W2 rows and b2 loaded together before the value stores (same aliasing as above)
-    float w2[kMaxP], b2[kMaxP];
-#pragma unroll
-    for (int q = 0; q < kMaxP; ++q) {
-      w2[q] = q < hd.P ? hd.w2[q * 64 + l] : 0.0f;
-      b2[q] = q < hd.P ? hd.b2[q] : 0.0f;
+    __syncthreads();
+    LNSTAMP(20, __builtin_amdgcn_s_memtime());
+    // pf = relu(policy 1x1 conv + bp) (channel-major), vfeat = relu(value 1x1 conv + bv), then
+    // v = tanh(W2 relu(W1 vfeat + b1) + b2); the 4 waves sweep quarters of W1's inputs
+    float* vfeat = hp + NN * 12;
+    float* part = vfeat + NN;
+    // the head biases in registers first: read inside the loop, each was re-loaded after every pf
+    // store (the compiler cannot rule out aliasing), one dependent round trip per store
+    const float bp0 = hd.bp[0], bp1 = hd.bp[1], bv0 = hd.bv[0];
+    for (int i = tid; i < NN; i += kLnThreads) {
+      const float* q = hp + i * 12;
+      const float p0 = ((q[0] + q[3]) + q[6]) + q[9], p1 = ((q[1] + q[4]) + q[7]) + q[10],
+                  pv = ((q[2] + q[5]) + q[8]) + q[11];
+      hd.pf[b * 2 * NN + i] = fmaxf(p0 + bp0, 0.0f);
+      hd.pf[b * 2 * NN + NN + i] = fmaxf(p1 + bp1, 0.0f);
+      vfeat[i] = fmaxf(pv + bv0, 0.0f);
     }
-    const float h = fmaxf(((part[l] + part[64 + l]) + (part[128 + l] + part[192 + l])) + hd.b1[l], 0.0f);
+    __syncthreads();
+    LNSTAMP(38, __builtin_amdgcn_s_memtime());
+    {
+      // wave w: inputs [Q w, Q (w + 1)) of W1 (L2-resident), every load issued before the first FMA
+      constexpr int Q = NN / 4;
+      static_assert(NN % 4 == 0, "k_leafnet_x3: quarters of the value-MLP inputs");
+      const int q0 = Q * wave;
+      float w[Q];
 #pragma unroll
-    for (int q = 0; q < kMaxP; ++q) {
-      if (q < hd.P) {
-        const float sum = wave_sum_f(w2[q] * h);
-        if (l == 0) hd.v[b * hd.P + q] = tanhf(sum + b2[q]);
+      for (int k = 0; k < Q; ++k) w[k] = hd.w1t[(size_t)(q0 + k) * 64 + l];
+      float a0 = 0.f, a1 = 0.f;
+      int k = 0;
+#pragma unroll
+      for (; k + 10 <= Q; k += 10) {
+#pragma unroll
+        for (int u = 0; u < 10; u += 2) {
+          a0 += w[k + u] * vfeat[q0 + k + u];
+          a1 += w[k + u + 1] * vfeat[q0 + k + u + 1];
+        }
+      }
+#pragma unroll
+      for (; k < Q; ++k) a0 += w[k] * vfeat[q0 + k];
+      part[wave * 64 + l] = a0 + a1;
+    }
+    __syncthreads();
+    LNSTAMP(39, __builtin_amdgcn_s_memtime());
+    if (wave == 0) {
+      // W2 rows and b2 loaded together before the value stores (same aliasing as above)
+      float w2[kMaxP], b2[kMaxP];
+#pragma unroll
+      for (int q = 0; q < kMaxP; ++q) {
+        w2[q] = q < hd.P ? hd.w2[q * 64 + l] : 0.0f;
+        b2[q] = q < hd.P ? hd.b2[q] : 0.0f;
+      }
+      const float h = fmaxf(((part[l] + part[64 + l]) + (part[128 + l] + part[192 + l])) + hd.b1[l], 0.0f);
+#pragma unroll
+      for (int q = 0; q < kMaxP; ++q) {
+        if (q < hd.P) {
+          const float sum = wave_sum_f(w2[q] * h);
+          if (l == 0) hd.v[b * hd.P + q] = tanhf(sum + b2[q]);
+        }
       }
     }
   }
@@ -651,6 +996,13 @@ static_assert(LnEdgeSched<20>::pos0(18) == 18 * 25 - 24, "LnEdgeSched<20>: 24 of
 // LnPixMap); read per launch, so one build compares the two (a captured graph keeps what it read)
 bool ln_edge() {
   const char* e = getenv("BK_LN_EDGE");
+  return e ? atoi(e) != 0 : true;
+}
+
+// BK_LN_FAST (default 1): the FAST instantiations (0: the others, the code as it was before them);
+// read per launch like BK_LN_EDGE
+bool ln_fast() {
+  const char* e = getenv("BK_LN_FAST");
   return e ? atoi(e) != 0 : true;
 }
 
@@ -698,22 +1050,18 @@ int ln_check(const bk_leafnet_args& a, const char* who, const float* out, bool r
 // t0 = 0: the kernel takes each row's tree and weights from the table in `in`.
 template <typename In>  // const float* (the planes of row t0), LnStates (at row t0) or LnRows
 int ln_launch(In in, int grid, const bk_leafnet_args& a, const LnNet& w, int t0, float* out, void* stream) {
-  const void* fns[3] = {(const void*)k_leafnet_x3<14, In>, (const void*)k_leafnet_x3<20, In>,
-                        (const void*)k_leafnet_x3<20, In, true>};
-  if (set_max_dynamic_lds(fns, 3, ln_lds_bytes(20)) != BK_OK) return BK_EHIP;
+  const void* fns[6] = {(const void*)k_leafnet_x3<14, In>,       (const void*)k_leafnet_x3<20, In>,
+                        (const void*)k_leafnet_x3<20, In, true>, (const void*)k_leafnet_x3<14, In, false, true>,
+                        (const void*)k_leafnet_x3<20, In, false, true>, (const void*)k_leafnet_x3<20, In, true, true>};
+  if (set_max_dynamic_lds(fns, 6, ln_lds_bytes(20)) != BK_OK) return BK_EHIP;
   const LnHeads h = ln_heads_of(a, w, t0);
   float* xout = out ? out + (size_t)t0 * a.N * a.N * 64 : nullptr;
   const dim3 g(grid), b(kLnThreads);
   hipStream_t s = (hipStream_t)stream;
-  if (a.N == 20 && ln_edge())
-    hipLaunchKernelGGL((k_leafnet_x3<20, In, true>), g, b, ln_lds_bytes(20), s, in, w.wstem, w.sstem, w.bstem, w.wt, w.st,
-                       w.bt, w.bounds, a.nlayers, h, xout);
-  else if (a.N == 20)
-    hipLaunchKernelGGL((k_leafnet_x3<20, In>), g, b, ln_lds_bytes(20), s, in, w.wstem, w.sstem, w.bstem, w.wt, w.st,
-                       w.bt, w.bounds, a.nlayers, h, xout);
-  else
-    hipLaunchKernelGGL((k_leafnet_x3<14, In>), g, b, ln_lds_bytes(14), s, in, w.wstem, w.sstem, w.bstem, w.wt, w.st,
-                       w.bt, w.bounds, a.nlayers, h, xout);
+  const int which = (a.N == 20 ? (ln_edge() ? 2 : 1) : 0) + (ln_fast() ? 3 : 0);
+  void* args[] = {(void*)&in,   (void*)&w.wstem,   (void*)&w.sstem,   (void*)&w.bstem, (void*)&w.wt, (void*)&w.st,
+                  (void*)&w.bt, (void*)&w.bounds, (void*)&a.nlayers, (void*)&h,       (void*)&xout};
+  (void)hipLaunchKernel(fns[which], g, b, args, ln_lds_bytes(a.N == 20 ? 20 : 14), s);
   return launch_check(std::is_same<In, LnRows>::value     ? "k_leafnet_x3 (rows)"
                       : std::is_same<In, LnStates>::value ? "k_leafnet_x3 (states)"
                                                           : "k_leafnet_x3");
@@ -741,6 +1089,17 @@ int bk_ln_stamps_clear() {
   return hipMemcpyToSymbol(HIP_SYMBOL(g_ln_stamps), zeros, sizeof(zeros)) == hipSuccess ? 0 : -1;
 }
 #endif
+
+int bk_ln_path_counts(int enable, unsigned* counts) {
+  unsigned cur[3];
+  if (hipMemcpyFromSymbol(cur, HIP_SYMBOL(g_ln_paths), sizeof(cur)) != hipSuccess) return BK_EHIP;
+  if (counts) {
+    counts[0] = cur[1];
+    counts[1] = cur[2];
+  }
+  const unsigned next[3] = {enable ? 1u : 0u, 0u, 0u};
+  return hipMemcpyToSymbol(HIP_SYMBOL(g_ln_paths), next, sizeof(next)) == hipSuccess ? BK_OK : BK_EHIP;
+}
 
 int bk_leafnet_x3_run(const bk_leafnet_args* a, int t0, int n, float* out, void* stream) {
   BK_REQUIRE(a && t0 >= 0 && n >= 0, "bk_leafnet_x3_run: bad argument");

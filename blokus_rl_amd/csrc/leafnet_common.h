@@ -34,7 +34,7 @@ using u32x2 = unsigned __attribute__((ext_vector_type(2)));
 #define BK_LN_STAMP 0  // timing diagnostics only: per-wave s_memtime stamps (bk_ln_stamps)
 #endif
 #if BK_LN_STAMP
-constexpr int kLnStamps = 32;
+constexpr int kLnStamps = 48;
 __device__ unsigned long long g_ln_stamps[256 * 4 * kLnStamps];
 #define LNSTAMP(i, v)                                                                                          \
   do {                                                                                                         \
@@ -90,7 +90,8 @@ __host__ __device__ constexpr int ln_plane(int N) { return ((N + 2) * ln_row(N) 
 // stem planes' region (dead after the stem) and above it: [group][256 threads] x 16 B
 __host__ __device__ constexpr int ln_x0_lds_groups(int N) { return N == 20 ? 7 : 0; }
 // LDS bytes of k_leafnet_x3<N>: 16 activation planes, then the 2 stem planes or the x0 stash
-// (whichever is larger), then the wave maxima (2 x 4 + 4 floats)
+// (whichever is larger), then the wave maxima (2 x 4 + 4 floats) and the waves' binary-board
+// flags (4 floats, k_leafnet_x3's FAST planes form)
 __host__ __device__ constexpr int ln_lds_body(int N) {
   return 16 * ln_plane(N) + (2 * ln_plane(N) > ln_x0_lds_groups(N) * 256 * 16 ? 2 * ln_plane(N)
                                                                                  : ln_x0_lds_groups(N) * 256 * 16);

@@ -424,7 +424,8 @@ def leafnet_x3_states(states, status: torch.Tensor | None, model: "LeafResNet", 
     """bk_leafnet_x3_states: packed states [B, 384] uint8 (N = the model's board) -> leafnet_x3's
     outputs on their observation planes, as float values, without the planes. status [B] int32
     (the search's leaf status) or None: rows whose status is not 1 are evaluated as the all-zero
-    observation and their state bytes are not read. states may also be the device address (int)
+    observation and their state bytes are not interpreted (the classic kernel loads them beside
+    the status and drops them: stale rows, but memory of the buffer). states may also be the device address (int)
     of a [B, 384] buffer the caller keeps alive (BatchedMCTS.leaf_states_ptr), with B = len(status)."""
     from .engine import STATE_BYTES
 

@@ -569,6 +569,11 @@ int bk_resnet_stem_tower_heads(const float* obs, int B, int N, int cin, const fl
  * and the three below are wrappers over bk_leafnet_x3_run, which refuses in their place. */
 int bk_leafnet_x3_weight_bytes(int cin);
 int bk_leafnet_x3_supported(int N);
+/* Test hook: which stem the planes form's workgroups took since the last call (BK_LN_FAST, the
+ * default). counts (may be null) receives {binary boards on the two-product stem, other boards on
+ * the full stem}; then the counters are cleared and counting is switched on (enable != 0) or off.
+ * Synchronizes the device. */
+int bk_ln_path_counts(int enable, unsigned* counts);
 int bk_leafnet_x3(const float* obs, int B, int N, int cin, const void* wstem, const float* sstem, const float* bstem,
                   int nlayers, const void* wtower, const float* stower, const float* btower, const float* bounds,
                   const float* wp, const float* bp, const float* wv, const float* bv, const float* w1t, const float* b1,
@@ -580,7 +585,8 @@ int bk_leafnet_x3(const float* obs, int B, int N, int cin, const void* wstem, co
  * product with its all-zero lo half is left out and adds exactly +-0). status (may be NULL): [B]
  * int32, the search's leaf status; a board whose status is not 1 is evaluated as the all-zero
  * observation (what the search writes for it in the planar form) and its state bytes are not
- * read. P = 4 (8 planes); the other operands as bk_leafnet_x3. */
+ * interpreted (they are loaded beside the status and dropped unless BK_LN_FAST=0: every row of
+ * states must be memory of the buffer). P = 4 (8 planes); the other operands as bk_leafnet_x3. */
 int bk_leafnet_x3_states(const void* states, const int32_t* status, int B, int N, int P, const void* wstem,
                          const float* sstem, const float* bstem, int nlayers, const void* wtower,
                          const float* stower, const float* btower, const float* bounds, const float* wp,

@@ -2,8 +2,11 @@
 events on the launch stream, and (--stamps, with BK_LIB=blokus_rl_amd/_lib/exp/liblnst.so from
 `make -C blokus_rl_amd/csrc lnstamps`) the per-wave phase times of one launch from its s_memtime
 stamps: 0 start, 1 stem input staged, 2 stem MFMAs done, 3 stem epilogue done, 4+2L / 5+2L layer
-L's MFMA loop / epilogue done (L < 8), 20 heads' partials, 29 end; 30/31 s_memrealtime (100 MHz).
-Usage: python tools/leafnet_bench.py [reps] [batch] [--stamps]"""
+L's MFMA loop / epilogue done (L < 8), 20 heads' partials, 29 end; 30/31 s_memrealtime (100 MHz);
+the fixed-cost phases of the stem (32 halo zeroed, 36 board maximum, 33 input converted and stored,
+34 epilogue pass, 35 its barrier) and of the heads (37 tower done, 38 pf pass, 39 value MLP sums).
+BK_LN_FAST=0 in the environment times the launch without the shorter stem, prologue and heads.
+Usage: python tools/leafnet_bench.py [reps] [batch] [--stamps] [--states]"""
 import ctypes
 import json
 import os
@@ -25,6 +28,17 @@ net = ResNet(20, 4, 30433, 5).cuda().eval()
 leaf = LeafResNet(net, normalize=False, features=True).eval()
 obs = (torch.rand((B, 8, 20, 20), device="cuda") < 0.3).float()
 st = torch.cuda.current_stream()
+if "--states" in sys.argv:  # the packed-state form on random mid-game boards
+    from blokus_rl_amd.boards import random_boards
+    from blokus_rl_amd.engine import Engine
+    from blokus_rl_amd.nets import leafnet_x3_states
+
+    obs = random_boards(Engine(20, 4, 5, device="cuda:0"), B, seed0=3)
+
+    def leafnet_x3(s, m):  # noqa: F811
+        return leafnet_x3_states(s, None, m)
+
+
 for _ in range(20):
     leafnet_x3(obs, leaf)
 torch.cuda.synchronize()
@@ -45,9 +59,10 @@ if "--stamps" in sys.argv:
     assert lib.bk_ln_stamps_clear() == 0
     leafnet_x3(obs, leaf)
     torch.cuda.synchronize()
-    s = np.zeros(256 * 4 * 32, dtype=np.uint64)
+    NS = 48  # kLnStamps
+    s = np.zeros(256 * 4 * NS, dtype=np.uint64)
     assert lib.bk_ln_stamps(s.ctypes.data_as(ctypes.c_void_p)) == 0
-    s = s.reshape(256, 4, 32).astype(np.int64)[:B]
+    s = s.reshape(256, 4, NS).astype(np.int64)[:B]
     t0 = s[:, :, 0:1]
     rel = s - t0
     clk = (s[:, :, 29] - s[:, :, 0]) / ((s[:, :, 31] - s[:, :, 30]) / 100e6) / 1e9
@@ -74,6 +89,18 @@ if "--stamps" in sys.argv:
         "chunks1_8": float(np.median(rel[:, :, 28] - rel[:, :, 27])),
         "chunks9_17": float(np.median(rel[:, :, 6] - rel[:, :, 28])),
     }
+    # the fixed-cost phases: each from the stamp before it in program order
+    order = [(0, None), (32, "halo_zero"), (36, "obs_wait_max_barrier"), (33, "convert_store"), (1, "stage_barrier"),
+             (2, "stem_mfma"), (34, "stem_epi_pass"), (35, "stem_epi_barrier"), (3, "stem_stash_write_barrier")]
+    fixed = {}
+    for (i0, _), (i1, nm) in zip(order, order[1:]):
+        fixed[nm] = float(np.median(rel[:, :, i1] - rel[:, :, i0]))
+    last = 5 + 2 * 7
+    fixed["layers8_9"] = float(np.median(rel[:, :, 37] - rel[:, :, last]))
+    for i0, i1, nm in ((37, 20, "heads_1x1_partials"), (20, 38, "heads_pf_pass"), (38, 39, "heads_mlp_sums")):
+        fixed[nm] = float(np.median(rel[:, :, i1] - rel[:, :, i0]))
+    fixed["heads_final_wave0"] = float(np.median(rel[:, 0, 29] - rel[:, 0, 39]))
+    res["fixed_cost_cycles_median"] = fixed
     res["total_cycles_median"] = float(np.median(rel[:, :, 29]))
     res["clock_ghz_median"] = float(np.median(clk))
     res["mfma_cycles_per_layer_floor"] = 18 * ng * 3 * 16
