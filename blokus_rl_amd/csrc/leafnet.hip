@@ -36,18 +36,8 @@
 #define BK_LN_VACC 1
 #include "leafnet_common.h"
 
-#ifndef BK_LN_EPIW
-#define BK_LN_EPIW 1  // a tower conv's outputs stored group by group inside its epilogue (0: all after it)
-#endif
-
 namespace bk {
 namespace {
-
-constexpr bool kLnEpiWrite = BK_LN_EPIW != 0;
-#ifndef BK_LN_IL
-#define BK_LN_IL 1  // the tower's B-fragment reads between the MFMAs of each triple (ln_chunk_il)
-#endif
-constexpr bool kLnInterleave = BK_LN_IL != 0;
 
 // The kernel's input form: the planar observation [B][8][N][N] f32 (as k_observe / the search
 // write it), or (STATES) the packed states it is made from, [B][kStateWords] words, with the
@@ -169,7 +159,7 @@ __global__ __launch_bounds__(kLnThreads, 1) void k_leafnet_x3(In in,
   // table in `in`. The other forms take the arguments as they are.
   constexpr bool ROWS = std::is_same<In, LnRows>::value;
   constexpr bool STATES = std::is_same<In, LnStates>::value || ROWS;
-  constexpr bool EDGE = EDGE_A && kLnInterleave;  // a BK_LN_IL=0 build keeps the old map and loop
+  constexpr bool EDGE = EDGE_A;
   const h16x8* __restrict__ wstem = wstem_a;
   const float* __restrict__ sstem = sstem_a;
   const float* __restrict__ bstem = bstem_a;
@@ -451,7 +441,7 @@ __global__ __launch_bounds__(kLnThreads, 1) void k_leafnet_x3(In in,
     };
     if (binary) {  // no lo plane: two products per chunk
       ln_prime_hi<NG>(rb, sin, ab, toff(0));
-      if constexpr (FAST && kLnInterleave) {
+      if constexpr (FAST) {
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the primed reads: the blocks below count their own
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
@@ -566,7 +556,7 @@ __global__ __launch_bounds__(kLnThreads, 1) void k_leafnet_x3(In in,
 
   f32x4 x0[NG];
   float max_in;
-  if constexpr (FAST && kLnEpiWrite) {
+  if constexpr (FAST) {
     // one pass: y (= x0[g], unscaled), y 2^ex_out (exact), its split halves, stored into the grid
     // as they are made: no wave reads the activation planes before the barrier below (the stem
     // reads its own two), so only the x0 stash, which reuses those two, waits for it; the stash is
@@ -694,36 +684,18 @@ __global__ __launch_bounds__(kLnThreads, 1) void k_leafnet_x3(In in,
           wq[sn][1] = wload(nl, cn - 18, 1);
         }
         const h16x8* w = wq[c % (kLnWpf + 1)];
-        if constexpr (kLnInterleave) {
-          if (c == 0)
-            ln_chunk_il<NG, true, PL>(acc, w[0], w[1], act, ab, coff_of(0), coff_of(1), rb);
-          else
-            ln_chunk_il<NG, false, PL>(acc, w[0], w[1], act, ab, coff_of(c), coff_of(c + 1 < 18 ? c + 1 : c), rb);
-        } else {
-          if (c == 0)
-            ln_chunk<NG, true, PL>(acc, w[0], w[1], act, ab, coff_of(0), coff_of(1), rb);
-          else
-            ln_chunk<NG, false, PL>(acc, w[0], w[1], act, ab, coff_of(c), coff_of(c + 1 < 18 ? c + 1 : c), rb);
-        }
+        if (c == 0)
+          ln_chunk_il<NG, true, PL>(acc, w[0], w[1], act, ab, coff_of(0), coff_of(1), rb);
+        else
+          ln_chunk_il<NG, false, PL>(acc, w[0], w[1], act, ab, coff_of(c), coff_of(c + 1 < 18 ? c + 1 : c), rb);
       }
     }
     // the last chunk's read-ahead (ln_chunk_il: untracked) lands before its registers are reused
-    if constexpr (kLnInterleave) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     ln_mfma_drain(acc);
     if (layer < 8) LNSTAMP(4 + 2 * layer, __builtin_amdgcn_s_memtime());
     const bool last = layer + 1 == nlayers;
-#ifndef BK_LN_ABL
-#define BK_LN_ABL 0  // timing diagnostics only (wrong outputs): 1 no grid writes or barriers between tower
-                     // convs, 2 = 1 without the epilogue arithmetic as well
-#endif
-    if (!last && BK_LN_ABL != 0) {
-      if constexpr ((BK_LN_ABL & 2) == 0) {
-        const int ex_out = scale_exp(bnd_a * max_in + bnd_b);
-        const float mx = epilogue(sv, bv, !(layer & 1), false, x0, true, ex_out);
-        max_in = fmaxf(max_in, mx);  // keep the arithmetic live
-        ex = ex_out;
-      }
-    } else if (!last && kLnEpiWrite) {
+    if (!last) {
       const int ex_out = scale_exp(bnd_a * max_in + bnd_b);  // = out_exp(layer + 1, max_in)
       if (layer == 1) LNSTAMP(21, __builtin_amdgcn_s_memtime());
       __syncthreads();  // every wave has finished reading the grid: the outputs go in place as made
@@ -731,20 +703,6 @@ __global__ __launch_bounds__(kLnThreads, 1) void k_leafnet_x3(In in,
       const float mx = epilogue(sv, bv, !(layer & 1), false, x0, true, ex_out, true);
       if (layer == 1) LNSTAMP(23, __builtin_amdgcn_s_memtime());
       post_max(mx, (layer + 1) & 1);
-      if (layer == 1) LNSTAMP(24, __builtin_amdgcn_s_memtime());
-      __syncthreads();
-      if (layer == 1) LNSTAMP(25, __builtin_amdgcn_s_memtime());
-      max_in = board_max((layer + 1) & 1);
-      ex = ex_out;
-    } else if (!last) {
-      const int ex_out = scale_exp(bnd_a * max_in + bnd_b);  // = out_exp(layer + 1, max_in)
-      const float mx = epilogue(sv, bv, !(layer & 1), false, x0, true, ex_out);
-      if (layer == 1) LNSTAMP(21, __builtin_amdgcn_s_memtime());
-      post_max(mx, (layer + 1) & 1);
-      if (layer == 1) LNSTAMP(22, __builtin_amdgcn_s_memtime());
-      __syncthreads();  // every wave has finished reading the grid
-      if (layer == 1) LNSTAMP(23, __builtin_amdgcn_s_memtime());
-      write_act();
       if (layer == 1) LNSTAMP(24, __builtin_amdgcn_s_memtime());
       __syncthreads();
       if (layer == 1) LNSTAMP(25, __builtin_amdgcn_s_memtime());

@@ -3,7 +3,8 @@ and bk_leafnet_x3_np_states: a row range writes its rows only, bitwise the whole
 four positional entries and nets.leafnet_x3 / leafnet_x3_states are that entry; its argument
 checks. Shapes: the classic kernel at N = 14, P = 4, B = 5 and the np kernel at N = 7, P = 2,
 B = 7 with np = 5 (four boards per workgroup: a range starting at row 1 packs other quads than the
-whole batch does) and np = 2 (one board per workgroup)."""
+whole batch does) and np = 2 (one board per workgroup). Last, the np kernel with one board per
+workgroup against the classic kernel at N = 14 and 20, P = 4, B = 3: bitwise the same outputs."""
 import ctypes
 import functools
 
@@ -89,33 +90,42 @@ def test_a_row_range_writes_its_rows_only_and_bitwise(family, np_, form, monkeyp
         assert torch.equal(p[1:4], w[1:4])
 
 
+def _positional(leaf, form, np_, obs, states, status, outs):
+    """The positional entry of `form` for the struct's np (0: the classic kernel, else the np
+    kernel with boards_per_wg = np - 1) on every row of obs / states, writing outs = (pf, v, tower
+    output)."""
+    from blokus_rl_amd.engine import _ptr, load_library
+
+    N, P = leaf.board_size, leaf.f.value_fc2.out_features
+    h = leaf.x3_heads
+    net = [_ptr(leaf.x3_wstem), _ptr(leaf.x3_sstem), _ptr(h[0]), 2 * len(leaf.f.blocks), _ptr(leaf.x3_wtower),
+           _ptr(leaf.x3_stower), _ptr(leaf.b_tower), _ptr(leaf.x3_bounds)] + [_ptr(t) for t in h[1:]]
+    outs = [_ptr(t) for t in outs]
+    bpw = [np_ - 1] if np_ else []
+    lib = load_library()
+    if form == "planar":
+        fn = lib.bk_leafnet_x3_np if np_ else lib.bk_leafnet_x3
+        rc = fn(_ptr(obs), obs.shape[0], N, 2 * P, *net, P, *outs, *bpw, None)
+    else:
+        fn = lib.bk_leafnet_x3_np_states if np_ else lib.bk_leafnet_x3_states
+        rc = fn(_ptr(states), _ptr(status), states.shape[0], N, P, *net, *outs, *bpw, None)
+    torch.cuda.synchronize()
+    return rc
+
+
 @pytest.mark.parametrize("form", FORMS)
 @pytest.mark.parametrize("family,np_", CONFIGS)
 def test_the_positional_entries_and_nets_are_the_entry(family, np_, form, monkeypatch):
-    from blokus_rl_amd.engine import _ptr, load_library
     from blokus_rl_amd.nets import leafnet_x3, leafnet_x3_states
 
     leaf, states, obs, status = _case(family)
-    B, N, P = states.shape[0], leaf.board_size, leaf.f.value_fc2.out_features
+    B, N = states.shape[0], leaf.board_size
     ref = _buffers(leaf, B)
     assert _run(_args(leaf, form, np_, ref[0], ref[1], monkeypatch), 0, B, ref[2]) == 0
     ref = [t[:B] for t in ref]
     # the positional entry of the form
     got = _buffers(leaf, B)
-    h = leaf.x3_heads
-    net = [_ptr(leaf.x3_wstem), _ptr(leaf.x3_sstem), _ptr(h[0]), 2 * len(leaf.f.blocks), _ptr(leaf.x3_wtower),
-           _ptr(leaf.x3_stower), _ptr(leaf.b_tower), _ptr(leaf.x3_bounds)] + [_ptr(t) for t in h[1:]]
-    outs = [_ptr(t) for t in got]
-    bpw = [np_ - 1] if np_ else []
-    lib = load_library()
-    if form == "planar":
-        fn = lib.bk_leafnet_x3_np if np_ else lib.bk_leafnet_x3
-        rc = fn(_ptr(obs), B, N, 2 * P, *net, P, *outs, *bpw, None)
-    else:
-        fn = lib.bk_leafnet_x3_np_states if np_ else lib.bk_leafnet_x3_states
-        rc = fn(_ptr(states), _ptr(status), B, N, P, *net, *outs, *bpw, None)
-    torch.cuda.synchronize()
-    assert rc == 0
+    assert _positional(leaf, form, np_, obs, states, status, got) == 0
     for g, r in zip(got, ref):
         assert torch.equal(g[:B], r) and bool((g[B:] == SENTINEL).all())
 
@@ -190,3 +200,42 @@ def test_argument_checks(monkeypatch):
     torch.cuda.synchronize()
     for family in bufs:
         assert all(bool((t == SENTINEL).all()) for t in bufs[family])
+
+
+@functools.lru_cache(maxsize=None)
+def _one_board_case(N):
+    """(leaf net of one block, planes [3, 8, N, N]: the all-zero observation, a binary board, dense
+    floats of magnitudes 1e-3..1e3; the first two as states [2, 384] with status (0, 1): a row
+    that is no leaf is the all-zero observation) on the N x N board, P = 4."""
+    from blokus_rl_amd.boards import random_boards
+    from blokus_rl_amd.engine import Engine
+    from blokus_rl_amd.nets import LeafResNet, ResNet
+
+    eng = Engine(N, 4, 5)
+    torch.manual_seed(100 + N)
+    net = ResNet(N, 4, eng.A, 1).cuda().eval()
+    leaf = LeafResNet(net, normalize=False, features=True, x3_boards="all").eval()
+    states = random_boards(eng, 2, seed0=5, max_plies=12).contiguous()
+    status = torch.tensor([0, 1], dtype=torch.int32, device="cuda")
+    obs = torch.zeros(3, 8, N, N, device="cuda")
+    obs[1] = eng.observe(states)[1]
+    g = torch.Generator(device="cuda").manual_seed(N)
+    sign = torch.randint(0, 2, (8, N, N), device="cuda", generator=g).float() * 2 - 1
+    obs[2] = sign * 10.0 ** (torch.rand(8, N, N, device="cuda", generator=g) * 6 - 3)
+    return leaf, obs.contiguous(), states, status
+
+
+@pytest.mark.parametrize("form", FORMS)
+@pytest.mark.parametrize("N", [14, 20])
+def test_np_with_one_board_per_workgroup_is_the_classic_kernel(N, form):
+    """bk_leafnet_x3_np with boards_per_wg = 1 and bk_leafnet_x3 (as launched by default) are the
+    same function where both apply (8 planes, 14x14 and 20x20): pf, v and the tower output of a
+    one-block net (one inner conv epilogue and the last one) agree bitwise."""
+    leaf, obs, states, status = _one_board_case(N)
+    B = obs.shape[0] if form == "planar" else states.shape[0]
+    classic, np1 = _buffers(leaf, B), _buffers(leaf, B)
+    assert _positional(leaf, form, 0, obs, states, status, classic) == 0
+    assert _positional(leaf, form, 2, obs, states, status, np1) == 0
+    assert bool((obs[1] != 0).any()) and bool((classic[0][:B] != SENTINEL).all())
+    for c, p in zip(classic, np1):
+        assert torch.equal(p, c)
