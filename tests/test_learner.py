@@ -179,6 +179,128 @@ def test_hip_policy_loss_matches_reference(tag):
     assert nz <= int(c["k"].sum())
 
 
+def _dev(t):
+    return t.cuda()
+
+
+def _loss_rows(ks, cap, A, seed, shift=0.0):
+    """Rows with raw counts ks (the kernels clamp them to [0, cap]) over A logits: logits 10 randn on
+    a 2^-10 grid (so that a shift by an integer is exact in f32) with column 0 non-negative and all
+    below 45, which keeps |lse| < 64 with and without a -60 shift; pi sums to 1 per row, to 0.7 in the
+    first row of two or more ids; ids (distinct within a row), pi and logits past K are live values
+    the kernels must not read. A == cap: the identity id map of sparse_policy_loss."""
+    g = torch.Generator().manual_seed(seed)
+    B = len(ks)
+    x = (10 * torch.randn(B, A, generator=g, dtype=torch.float64) * 1024).round() / 1024
+    x[:, 0] = x[:, 0].abs()
+    x = x.clamp(max=45.0) + shift
+    k = torch.tensor(ks, dtype=torch.int32)
+    kc = k.clamp(0, cap)
+    if A == cap:
+        ids = torch.arange(cap, dtype=torch.int16).expand(B, cap).contiguous()
+    else:
+        perm = torch.rand(B, A, generator=g).argsort(1)
+        rows = torch.arange(B)
+        perm[rows, (perm == 0).nonzero()[:, 1]] = perm[:, 0]  # id 0 (the non-negative column) first
+        perm[:, 0] = 0
+        ids = perm[:, :cap].to(torch.int16).contiguous()
+    pi = torch.rand(B, cap, generator=g, dtype=torch.float64) + 0.01
+    valid = torch.arange(cap)[None, :] < kc[:, None]
+    tot = (pi * valid).sum(1, keepdim=True).clamp_min(1e-9)
+    target = torch.ones(B, 1, dtype=torch.float64)
+    two = (kc >= 2).nonzero()
+    if len(two):
+        target[int(two[0])] = 0.7
+    pi = (pi / tot * target).float()
+    assert x.float().double().equal(x)
+    return x.float(), ids, pi, k, kc, valid
+
+
+def _loss_ref(x, ids, pi, kc, c=1.0):
+    """c * torch_sparse_policy_loss in fp64 (with the clamped counts) -> loss, gradient, lse."""
+    xr = x.double().requires_grad_()
+    loss = c * torch_sparse_policy_loss(xr, ids, pi.double(), kc)
+    loss.backward()
+    valid = torch.arange(ids.shape[1])[None, :] < kc.long()[:, None]
+    lse = torch.logsumexp(torch.gather(x.double(), 1, ids.long()).masked_fill(~valid, float("-inf")), 1)
+    lse = torch.where(kc > 0, lse, torch.zeros_like(lse))
+    assert float(lse.abs().max()) < 64.0  # the range these tests keep to (see the docstrings)
+    assert bool(torch.isfinite(xr.grad).all())
+    return float(loss.detach()), xr.grad
+
+
+def _grad_ratio(g, ref, c):
+    """Largest |g - ref| / (2e-7 c + 2e-5 |ref|): the bars of test_hip_policy_loss_matches_reference
+    (assert_allclose's atol + rtol |ref|), the absolute part scaled by the upstream factor c."""
+    return float(((g.double() - ref).abs() / (2e-7 * c + 2e-5 * ref.abs())).max())
+
+
+def _listed(ids, valid, A):
+    m = torch.zeros(ids.shape[0], A, dtype=torch.bool)
+    m.scatter_(1, ids.long(), valid)
+    return m
+
+
+@pytest.mark.gpu
+def test_hip_policy_loss_upstream_scale_and_clamp():
+    """(2.5 * policy_loss).backward(): k_policy_loss_grad's device-side upstream factor with a value
+    that is not 1, on dense logits with K = 0, 1, 9, cap, k > cap (read as cap) and k < 0 (read as
+    0), against the fp64 restatement; the gradient off the first K listed ids stays exactly zero.
+    |lse| < 64 here: lse is stored as one f32, so the gradient's relative error grows as half an ulp
+    of |lse| (below 2e-6 in this range); larger logits are not tested."""
+    from blokus_rl_amd.alphazero.learner import policy_loss
+
+    cap, A, c = 64, 300, 2.5
+    x, ids, pi, k, kc, valid = _loss_rows([0, 1, 9, cap, cap + 7, -3, 30], cap, A, 41)
+    ref_loss, ref_g = _loss_ref(x, ids, pi, kc, c)
+    xd = _dev(x).requires_grad_()
+    loss = c * policy_loss(xd, _dev(ids), _dev(pi), _dev(k))
+    loss.backward()
+    r_loss = abs(float(loss.detach()) - ref_loss) / (2e-5 * abs(ref_loss))
+    r_g = _grad_ratio(xd.grad.cpu(), ref_g, c)
+    print(f"policy loss x2.5: loss {r_loss:.4f} grad {r_g:.4f}")
+    assert r_loss <= 1.0 and r_g <= 1.0, (r_loss, r_g)
+    listed = _listed(ids, valid, A)
+    assert int(listed.sum()) == int(kc.sum())
+    assert bool((xd.grad.cpu()[~listed] == 0).all()), "gradient off the first K listed ids"
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("cap", [64, 1024])
+@pytest.mark.parametrize("B", [1, 4, 5, 7])
+def test_hip_sparse_policy_loss_matches_fp64(B, cap):
+    """sparse_policy_loss on [B, cap] logits (the identity id map, ldx == cap) against the fp64
+    restatement: B around the 4-rows-per-block launch, K = 0, 1, 63, 64, 65 and cap, k > cap and
+    k < 0, a row with sum(pi) = 0.7; logits 10 randn and the same shifted by -60 match the reference
+    and each other (the loss and its gradient do not move under a shift) within the same bars.
+    |lse| < 64 here: lse is stored as one f32, so the gradient's relative error grows as half an ulp
+    of |lse| (below 2e-6 in this range); larger logits are not tested."""
+    from blokus_rl_amd.alphazero.learner import sparse_policy_loss
+
+    ks_all = [65, 0, 1, 63, 64, cap, cap + 5, -2]  # min(65, cap) ids at cap = 64
+    worst = {"loss": 0.0, "grad": 0.0, "shift loss": 0.0, "shift grad": 0.0}
+    for i in range(0, len(ks_all), B):
+        ks = [ks_all[(i + j) % len(ks_all)] for j in range(B)]
+        got = {}
+        for shift in (0.0, -60.0):
+            x, ids, pi, k, kc, valid = _loss_rows(ks, cap, cap, 50 + i, shift)
+            ref_loss, ref_g = _loss_ref(x, ids, pi, kc)
+            xd = _dev(x).requires_grad_()
+            loss = sparse_policy_loss(xd, _dev(pi), _dev(k))
+            loss.backward()
+            g = xd.grad.cpu()
+            got[shift] = (float(loss.detach()), g)
+            worst["loss"] = max(worst["loss"], abs(got[shift][0] - ref_loss) / (2e-5 * abs(ref_loss) + 1e-300))
+            worst["grad"] = max(worst["grad"], _grad_ratio(g, ref_g, 1.0))
+            assert bool((g[~valid] == 0).all())  # off the first K columns: exactly zero
+        (l0, g0), (l1, g1) = got[0.0], got[-60.0]
+        worst["shift loss"] = max(worst["shift loss"], abs(l1 - l0) / (2e-5 * abs(l0) + 1e-300))
+        worst["shift grad"] = max(worst["shift grad"], _grad_ratio(g1, g0.double(), 1.0))
+    print(f"sparse policy loss B={B} cap={cap}: " + " ".join(f"{n} {v:.4f}" for n, v in worst.items()))
+    for n, v in worst.items():
+        assert v <= 1.0, (n, v)
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("preset,ids_cap", [((20, 4, 5), 1024), ((14, 2, 5), 1024), ((7, 2, 5), 256)],
                          ids=["20x4x5", "14x2x5", "7x2x5"])
