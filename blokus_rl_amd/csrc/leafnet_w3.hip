@@ -59,7 +59,7 @@ __device__ __forceinline__ int w3_swz(int C) { return ((C - 1) >> 1) & 7; }
 #endif
 
 #if BK_LN_STAMP
-// timing diagnostics only (make w3stamps): per-wave s_memtime stamps of one launch, tools/w3/stamps_w3.py
+// timing diagnostics only (make lnstamps): per-wave s_memtime stamps of one launch, tools/w3/stamps_w3.py
 __device__ unsigned long long g_w3_stamps[256 * 4 * 128];
 #define W3STAMP(i)                                                                                         \
   do {                                                                                                     \

@@ -1,4 +1,4 @@
-"""k_vec_step7 phase cycles (diagnostic build: tools/build_lib_variant.sh vecst -DBK_VEC_STAMP, then
+"""k_vec_step7 phase cycles (diagnostic build: make -C blokus_rl_amd/csrc vecstamps, then
 BK_LIB=blokus_rl_amd/_lib/exp/libvecst.so): per wave, s_memtime at 0 start, 1 state loaded + the
 agent's legal origins, 2 agent placed + advance, 3 opponent moves done, 4 the agent's final legal
 origins, 5 stores + LDS staging, 6 after the barrier, 7 end. Medians / max over the waves of the

@@ -1,5 +1,5 @@
 """Per-wave phase times of one k_leafnet_w3 launch from its s_memtime stamps (BK_LIB =
-blokus_rl_amd/_lib/exp/libw3st.so from `make -C blokus_rl_amd/csrc w3stamps`), 256 boards 20x20,
+blokus_rl_amd/_lib/exp/liblnst.so from `make -C blokus_rl_amd/csrc lnstamps`), 256 boards 20x20,
 ResNet-5x64: stem, layer 1 unit by unit (issue time from the barrier to the next barrier, and the
 wait at each barrier), the layer end, the tower, the heads; medians over the 1024 waves.
 Usage: BK_LIB=... python tools/w3/stamps_w3.py"""
