@@ -142,9 +142,12 @@ __device__ __forceinline__ void wave_argmax(double& best, int& bi) {
 }
 
 // PUCT choice at a node (mcts.py:41-46): argmax_i Q_i + cpuct*P_i*sqrt(sum N + 1e-6)/(1+N_i);
-// also returns the chosen child's action id. Up to kSelB * 64 children (every 20x20 node) in one
-// memory round trip: each lane loads all its children's (P, N, Q, id) first, the visit sum is
-// the wave's integer sum of N, then the lane scans its children in index order.
+// also returns the chosen child's action id. Up to kSelB * 64 = 768 children in one memory round
+// trip: each lane loads all its children's (P, N, Q, id) first, the visit sum is the wave's integer
+// sum of N, then the lane scans its children in index order. Random playouts stay below 768 on
+// every preset but 2-player 20x20 (up to 907 there; 699 with 4 players, 661 / 454 on 14x14, 231 on
+// 7x7), and a player that keeps its mobility goes higher on any 14x14 or 20x20 board (thousands on
+// scattered boards): those nodes take the two-pass branch below.
 constexpr int kSelB = 12;
 // waves that take orientations in a leaf bitmask (the rest idle): 8 slices (every 8th
 // orientation) — each claiming wave pays its own row context, so 16 slices cost more setup than

@@ -8,7 +8,16 @@ preset. Every simulation: the oracle's outcome (the leaf's board hash, or a term
 leaf's legal bitmask and the observation planes select() writes (N = 14 and N = 5 take its scalar
 row writer). After each of two moves on the reused tree: root ids, N, Q (float64), P,
 root_policy at T = 1 and T = 0, the visited children of every oracle node reached from the root,
-and the chosen action's next state. All comparisons are equality."""
+and the chosen action's next state. All comparisons are equality.
+
+Roots named ("bigk", K) are the big-K fixture's states (tests/golden/make_bigk_states.py) with
+K = 769, 2049 and 5056 legal moves on 2-player 20x20 and 2374 on 2-player 14x14: above
+kSelB * 64 = 768 children select_child takes its two-pass branch (the visit sum, then the scan),
+and above kExpandLdsIds = 2048 the expansion compacts the ids straight into the child pool. Their
+stand-in net (prior_value_tail) puts the largest prior on the last child, so the first descent
+from such a root must pick child K - 1 — a scan that stopped short of the tail picks another —
+and the cases assert that a root child of index >= 768 is visited and that a node below the root
+with more than 768 children is expanded and descended through."""
 from collections import defaultdict
 from functools import lru_cache
 
@@ -16,14 +25,16 @@ import numpy as np
 import pytest
 import torch
 
+import bigk_util
 from mcts_golden_util import prior_value
 from oracle.oracle import MCTSOracle, Oracle
 
 pytestmark = pytest.mark.gpu
 
 MOVES = 2
-# (preset, root: None = the initial state, else random_board(seed, max_plies), sims, cpuct,
-#  the oracle reaches terminal leaves)
+BIG = 768  # kSelB * 64
+# (preset, root: None = the initial state, ("bigk", K) = the fixture state of that K, else
+#  random_board(seed, max_plies), sims, cpuct, the oracle reaches terminal leaves)
 CASES = [
     ((14, 4, 5), None, 60, 1, False),
     ((14, 4, 5), (5, 30), 80, 2, False),
@@ -31,7 +42,30 @@ CASES = [
     ((20, 2, 5), (9, 36), 80, 1, False),
     ((20, 4, 4), (2, 30), 120, 1, False),
     ((5, 2, 5), None, 100, 1, True),
+    ((20, 2, 5), ("bigk", 769), 60, 1, False),
+    ((20, 2, 5), ("bigk", 2049), 50, 1, False),
+    ((20, 2, 5), ("bigk", 5056), 40, 1, False),
+    ((14, 2, 5), ("bigk", 2374), 50, 1, False),
 ]
+
+
+def _is_bigk(k: int) -> bool:
+    return CASES[k][1] is not None and CASES[k][1][0] == "bigk"
+
+
+def prior_value_tail(h: int, K: int, P: int):
+    """prior_value with the largest logit moved to the last child."""
+    rng = np.random.default_rng(h & 0x7FFFFFFFFFFFFFFF)
+    x = rng.standard_normal(K).astype(np.float32)
+    x[K - 1] = x.max() + np.float32(2.0)
+    e = np.exp(x - x.max()).astype(np.float32)
+    p = (e / e.sum()).astype(np.float32)
+    v = rng.uniform(-1.0, 1.0, P).astype(np.float32)
+    return p, v
+
+
+def _prior(k: int):
+    return prior_value_tail if _is_bigk(k) else prior_value
 
 
 def _groups():
@@ -58,11 +92,16 @@ def _expected(k: int):
     def evaluate(s, player):
         leaves.append(o.hash(s))
         ids = o.legal_ids(s, player)
-        p, v = prior_value(o.hash(s), len(ids), o.P)
+        p, v = _prior(k)(o.hash(s), len(ids), o.P)
         return ids, p, v.astype(np.float64)
 
     m = MCTSOracle(o, evaluate)
-    s = o.init_state() if root is None else o.random_board(*root)
+    if root is None:
+        s = o.init_state()
+    elif root[0] == "bigk":
+        s = bigk_util.state_named(preset, root[1])
+    else:
+        s = o.random_board(*root)
     moves = []
     for _ in range(MOVES):
         assert o.game_ended(s) is None
@@ -111,7 +150,12 @@ def test_batched_mcts_matches_oracle(group):
             assert hits > 0  # the terminal-score backup is exercised
     cases = [mv for mv, _ in expected]
     sims = [CASES[k][2] for k in case_ids]
-    m = BatchedMCTS(eng, T, node_cap=4096, child_cap=T * 4096 * (700 if preset[0] >= 14 else 200))
+    # the child pool per tree: the presets' usual size, or for fixture roots every expanded node (one
+    # a simulation) at twice the largest root's K; the rows read back hold the largest node
+    big_k = max([CASES[k][1][1] for k in case_ids if _is_bigk(k)], default=0)
+    per_tree = max(4096 * (700 if preset[0] >= 14 else 200), (MOVES * max(sims) + 1) * 2 * big_k)
+    cap = 8192 if big_k else 2048
+    m = BatchedMCTS(eng, T, node_cap=4096, child_cap=T * per_tree)
     logp = torch.zeros((T, eng.A), dtype=torch.float32, device=dev)
     vals = torch.zeros((T, eng.P), dtype=torch.float32, device=dev)
     for r in range(MOVES):
@@ -135,14 +179,14 @@ def test_batched_mcts_matches_oracle(group):
                     ids = _bits_to_ids(mask_h[t], eng.A)
                     assert (ids == o.legal_ids(leaves_h[t])).all()
                     assert (obs_h[t] == o.observe(leaves_h[t])).all(), (r, sim, t)
-                    p, v = prior_value(want, len(ids), eng.P)
+                    p, v = _prior(case_ids[t])(want, len(ids), eng.P)
                     logp[t, torch.from_numpy(ids).to(dev)] = torch.from_numpy(p).to(dev)
                     vals[t] = torch.from_numpy(v).to(dev)
             m.expand_backup(logp, vals, prior_mode=1)
         m.check()
-        ids, n, q, p, counts = (x.cpu().numpy() for x in m.root_stats(roots, None, cap=2048))
-        pid, pi1, pc = (x.cpu().numpy() for x in m.root_policy(roots, None, 1.0))
-        _, pi0, _ = (x.cpu().numpy() for x in m.root_policy(roots, None, 0.0))
+        ids, n, q, p, counts = (x.cpu().numpy() for x in m.root_stats(roots, None, cap=cap))
+        pid, pi1, pc = (x.cpu().numpy() for x in m.root_policy(roots, None, 1.0, cap=cap))
+        _, pi0, _ = (x.cpu().numpy() for x in m.root_policy(roots, None, 0.0, cap=cap))
         for t, c in enumerate(cases):
             mv = c[r]
             K = int(counts[t])
@@ -153,12 +197,21 @@ def test_batched_mcts_matches_oracle(group):
             assert p[t, :K].astype(np.float64).tolist() == mv["P"]
             assert pi1[t, :K].tolist() == mv["d1"]
             assert pi0[t, :K].tolist() == mv["d0"]
+            if _is_bigk(case_ids[t]) and r == 0:
+                # both passes of select_child's two-pass branch decided something: the scan reached the
+                # root's tail, and a node above 768 children below the root was expanded and scanned
+                assert K == CASES[case_ids[t]][1][1] and n[t, K - 1] > 0 and n[t, BIG:K].sum() > 0
+                below = [(Kn, len(visited)) for _, Kn, visited in mv["nodes"][1:] if Kn > BIG]
+                print(f"case {case_ids[t]}: K {K}, visited root children >= {BIG}: {int((n[t, BIG:K] > 0).sum())}, "
+                      f"nodes below the root above {BIG} children: {len(below)}, descended through: "
+                      f"{sum(1 for _, nv in below if nv)}")
+                assert below and any(nv for _, nv in below)
             only = torch.zeros(T, dtype=torch.int32, device=dev)
             only[t] = 1
             for state, Kn, visited in mv["nodes"]:
                 node_roots = roots.clone()
                 node_roots[t] = torch.from_numpy(state).to(dev)
-                _, nn_, qq, _, cc = m.root_stats(node_roots, only, cap=2048)
+                _, nn_, qq, _, cc = m.root_stats(node_roots, only, cap=cap)
                 assert int(cc[t]) == Kn
                 nh, qh = nn_[t, :Kn].cpu().numpy(), qq[t, :Kn].cpu().numpy()
                 assert [[i, int(nh[i]), float(qh[i])] for i in range(Kn) if nh[i] > 0] == visited
